@@ -18,6 +18,8 @@ Prints ONE JSON line: metric = accepted ODE steps/s summed over the ensemble (ne
                  reference's published single-solve time beside them.
 Extra keys (not `value`): the same job host-driven over the trait operations (lock-step over the whole ensemble), per-member control,
 and a 1.6M-member ensemble that fills the chip.
+cpu_baseline, the extra keys, the trait-path pass and the other BASELINE configs (`configs`) are measured under --full only: a plain run sets up, warms up,
+times --steps solves, writes the last step's outputs under --dump-outputs DIR, and prints the line (value, ms_per_step, roofline).
 """
 import argparse
 import json
@@ -647,6 +649,25 @@ class _CpuStub:
                 "number_of_linear_solver_setups": 70 * self.nbatch, "failed_members": 0}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, trajectory, counters, seed=2024):
+    """--dump-outputs: trajectory [save points x states x members] and the solve counters of the last timed step -> d/<name>.npy, float64.  A trajectory larger
+    than the limit is cut to a fixed seeded sample of members (sorted; their indices in trajectory_members.npy)."""
+    os.makedirs(d, exist_ok=True)
+    y = np.asarray(trajectory, dtype=np.float64)
+    out = {"trajectory": y, "solve_counters": np.asarray(counters, dtype=np.float64)}
+    if y.nbytes > DUMP_LIMIT_BYTES:
+        per_member = y.nbytes // y.shape[-1]
+        keep = max(1, (DUMP_LIMIT_BYTES - (1 << 20)) // (per_member + 8))
+        idx = np.sort(np.random.default_rng(seed).choice(y.shape[-1], size=keep, replace=False))
+        out["trajectory"] = np.ascontiguousarray(y[..., idx])
+        out["trajectory_members"] = idx.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def _relaunch_under_torchrun(args):
     """`python bench.py --gpus N` outside a launcher: become `python -m torch.distributed.run --nproc-per-node N bench.py ...` (one rank per GPU)."""
     s = socket.socket()
@@ -688,6 +709,12 @@ def main():
                     help="--config c4: torch = torch.distributed all_gather_into_tensor (RCCL); cabi = the library's own dsh_gather_batch_axis (csrc/dsh_dist.hip: librccl bound "
                          "by libdiffsol_hip.so, what a Rust / C caller uses), the 128-byte id broadcast through torch's store")
     ap.add_argument("--cpu-stub", action="store_true", help="TEST HOOK: no GPU, gloo backend, stub solver (exercises launcher + aggregation only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the extra passes, the CPU baseline, BASELINE configs[2..4] and the trait-path pass "
+                         "(each can still be left out with its --no-* flag).  Without it a run sets up, warms up, times --steps solves and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float64; a seeded sample of the members when the "
+                         "whole exceeds 64 MB): trajectory[save point, state, member] and solve_counters")
     args = ap.parse_args()
     assert args.gpus >= 1 and args.steps >= 1 and args.warmup >= 0
 
@@ -798,6 +825,8 @@ def main():
         pend[0] = pend[1] = None
         return y_last
 
+    last_tot = [None]  # counters of the newest step of the newest timed pass (--dump-outputs)
+
     def timed(k, step):
         barrier()
         t0 = time.perf_counter()
@@ -807,6 +836,7 @@ def main():
             tot, y = step()
             for key, v in tot.items():
                 acc[key] = acc.get(key, 0) + v
+            last_tot[0] = tot
         if overlap:
             yd = drain()
             y = yd if yd is not None else y
@@ -835,11 +865,17 @@ def main():
     finite = bool(torch.isfinite(y).all().item())
     mass_err = float((y.sum(dim=1) - 1.0).abs().max().item()) if not stub else 0.0
 
-    y_value_pass = y.clone() if not stub else None  # the extras below reuse the output buffer
+    if args.dump_outputs:
+        counter_keys = ("number_of_steps", "number_of_nonlinear_solver_iterations", "number_of_linear_solver_setups", "failed_members")
+        counters = allreduce([0.0] + [float(last_tot[0][k]) for k in counter_keys])[1:]  # summed over ranks: the counters of the whole ensemble
+        if rank == 0:
+            dump_outputs(args.dump_outputs, y.cpu().numpy(), counters)
 
-    # ------------------------------------------------------------------ extra passes (never `value`)
+    y_value_pass = y.clone() if not stub and args.full else None  # the extras below reuse the output buffer
+
+    # ------------------------------------------------------------------ extra passes (never `value`; --full only)
     extras = {}
-    if not stub and not args.no_extras:
+    if not stub and args.full and not args.no_extras:
         k_x = min(args.steps, 5)
 
         def mode_pass(mode, with_reset):
@@ -1024,10 +1060,10 @@ def main():
         else:
             rec["roofline"] = None
         rec.update(extras)
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if world == 1 and args.full and not args.no_cpu_baseline and not stub:
             big_sample = robertson_params(max(args.cpu_sample, n_total))  # same distribution, same seed, a longer draw
             rec["cpu_baseline"] = cpu_baseline(big_sample, args.cpu_sample)
-        if world == 1 and not stub and not args.no_configs:
+        if world == 1 and not stub and args.full and not args.no_configs:
             del solver
             try:
                 rec["trait_path"] = bench_trait_path(params[lo:hi], local_rank, 3)
@@ -1110,6 +1146,12 @@ def main_c4(args, rank, local_rank, world, stub):
             acc[k] = acc.get(k, 0) + v
     barrier()
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        c = torch.tensor([float(tot[k]) for k in ("number_of_steps", "number_of_nonlinear_solver_iterations", "failed_members")], dtype=torch.float64, device=dev)
+        if world > 1:
+            dist.all_reduce(c, op=dist.ReduceOp.SUM)  # the counters of the whole ensemble
+        if rank == 0:
+            dump_outputs(args.dump_outputs, y.cpu().numpy(), c.tolist())
     a = torch.tensor([el, acc["number_of_steps"], acc["number_of_nonlinear_solver_iterations"], acc["failed_members"]], dtype=torch.float64, device=dev)
     if world > 1:
         tmax = a[:1].clone()

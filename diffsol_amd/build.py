@@ -20,6 +20,7 @@ def build(verbose=False, jobs=8):
 
 
 MANIFEST_DIR = os.path.join(_HERE, "jit_manifest")
+MAX_REPLAY_JOBS = 12
 
 
 def replay_manifests(jobs=None, verbose=False, only=None, budget_s=420.0, preload_torch=False):
@@ -43,7 +44,9 @@ def replay_manifests(jobs=None, verbose=False, only=None, budget_s=420.0, preloa
         files.append(out)
     if not files:
         return 0, 0
-    jobs = jobs or max(1, min(len(os.sched_getaffinity(0)), 16))
+    # at most MAX_REPLAY_JOBS workers: each one loads the HIP runtime and may hold the device open, and so may the calling process (build() precompiles before it
+    # replays); together they stay below 16 processes with the device open
+    jobs = jobs or max(1, min(len(os.sched_getaffinity(0)), MAX_REPLAY_JOBS))
     # worker k compiles requests k, k + jobs, ... of every manifest, one dsh_jit_replay call per request, and starts no new one after the deadline (what is left is
     # compiled at first use, as before)
     # preload_torch: PyTorch-ROCm bundles its own HIP runtime / hiprtc (another ROCm release than /opt/rocm); a process that imports torch first resolves the library's

@@ -18,7 +18,7 @@ else
   mkdir -p gpurun_out/r04
   for d in "" diffsol_amd/lib_exp/w2_p1 diffsol_amd/lib_exp/w3_p1 diffsol_amd/lib_exp/w4_p1; do
     echo "== ${d:-default (2 waves per SIMD, swap partner in LDS)}"
-    DSH_LIB_DIR=${d:+$PWD/$d} python bench.py --no-cpu-baseline --no-configs --steps 10 --warmup 2 2>/dev/null | python -c "
+    DSH_LIB_DIR=${d:+$PWD/$d} python bench.py --full --no-cpu-baseline --no-configs --steps 10 --warmup 2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(json.dumps({'value': d['value'], 'ms_per_step': d['ms_per_step'], 'per_member_ms': d['per_member']['ms_per_step'], 'large_ensemble_steps_per_s': d['large_ensemble']['ode_steps_per_sec'], 'large_kernel_ms': d['large_ensemble']['kernel_ms'], 'failed': d['checks']['failed_members']}))"

@@ -17,9 +17,13 @@ This script
      and that each associated type with a trait bound names a shim type that implements that trait (recursively with ITS marker bounds).
 
     python scripts/rust_bound_check.py [shim_src_dir]      # prints violations, exit 1 if any
+    python scripts/rust_bound_check.py --traits tests/golden/reference_traits.json [shim_src_dir]   # the same against the recorded trait bounds
+    python scripts/rust_bound_check.py --record tests/golden/reference_traits.json                  # re-record them from the reference checkout
 
-It reads /root/reference (present in the build container only); tests/test_rust_shim.py skips the reference-dependent part elsewhere.
+Step 1 needs the reference checkout (REF).  Its result is names only (traits, supertraits, marker bounds, associated types and their bounds, file:line), and
+tests/golden/reference_traits.json holds it, so that tests/test_rust_shim.py runs without the checkout.
 """
+import json
 import os
 import re
 import sys
@@ -235,8 +239,19 @@ class Shim:
         return False, f"neither derived nor implemented ({st['file'] if st else 'unknown type'})"
 
 
-def check(src_dir, ref=REF):
-    traits = parse_reference_traits(ref)
+def save_traits(traits, path):
+    with open(path, "w") as f:
+        json.dump({k: dict(v, markers=sorted(v["markers"])) for k, v in sorted(traits.items())}, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+def load_traits(path):
+    with open(path) as f:
+        return {k: dict(v, markers=set(v["markers"])) for k, v in json.load(f).items()}
+
+
+def check(src_dir, ref=REF, traits=None):
+    traits = parse_reference_traits(ref) if traits is None else traits
     shim = Shim(src_dir)
     bad, checked = [], 0
     done = set()
@@ -293,8 +308,18 @@ def check(src_dir, ref=REF):
 
 def main():
     args = [a for a in sys.argv[1:] if a != "-v"]
+    opts = {}
+    while args and args[0] in ("--traits", "--record"):
+        opts[args[0]] = args[1]
+        args = args[2:]
+    if "--record" in opts:
+        traits = parse_reference_traits()
+        assert traits, f"no reference traits under {REF}"
+        save_traits(traits, opts["--record"])
+        print(f"{len(traits)} reference traits -> {opts['--record']}")
+        return 0
     src = args[0] if args else os.path.join(ROOT, "rust", "diffsol-hip", "src")
-    bad, checked, traits, shim = check(src)
+    bad, checked, traits, shim = check(src, traits=load_traits(opts["--traits"]) if "--traits" in opts else None)
     if "-v" in sys.argv:
         print("\n".join(shim.log))
     print(f"{len(traits)} reference traits parsed, {len(shim.structs)} shim types, {checked} marker / associated-type bounds checked")

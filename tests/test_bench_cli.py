@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -98,3 +100,33 @@ def test_compact_line_of_a_full_shape_record_fits_4k():
     for i in range(12):
         fat["configs"][f"extra_config_number_{i}"] = {"error": "e" * 3000}
     assert len(bench.compact_line(fat)) <= 4096
+
+
+def test_dump_outputs_writes_the_last_steps_arrays_and_repeats_them(tmp_path):
+    """--dump-outputs DIR: the trajectory of the last timed step and its counters as float64 .npy files, the same from run to run with the same arguments;
+    --full is accepted beside it, and --steps is the number of timed steps the line reports."""
+    runs = []
+    for k, extra in enumerate(([], ["--full"])):
+        d = tmp_path / f"run{k}"
+        r = _run(["--steps", "3", "--warmup", "1", "--nb", "64", "--cpu-stub", "--dump-outputs", str(d)] + extra)
+        assert r.returncode == 0, r.stderr[-2000:]
+        rec = _json_line(r.stdout)
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        y, c = np.load(d / "trajectory.npy"), np.load(d / "solve_counters.npy")
+        assert y.dtype == np.float64 and y.shape == (7, 3, 64) and np.isfinite(y).all()
+        assert c.dtype == np.float64 and c.tolist() == [300 * 64, 700 * 64, 70 * 64, 0]
+        runs.append((y, c))
+    assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][1], runs[1][1])
+
+
+def test_dump_outputs_cuts_a_large_trajectory_to_a_fixed_sample(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 << 20)
+    y = np.arange(7 * 3 * 100_000, dtype=np.float64).reshape(7, 3, 100_000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), y, [1.0, 2.0])
+    ya, ia = np.load(tmp_path / "a" / "trajectory.npy"), np.load(tmp_path / "a" / "trajectory_members.npy")
+    assert ya.nbytes <= 2 << 20 and ya.shape[:2] == (7, 3) and ya.shape[2] == ia.size and ia.dtype == np.float64
+    assert np.array_equal(ya, y[..., ia.astype(np.int64)])
+    assert np.array_equal(ya, np.load(tmp_path / "b" / "trajectory.npy"))

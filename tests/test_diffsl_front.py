@@ -1,5 +1,6 @@
 """DiffSL front end (diffsol_amd/host/diffsl.hpp) on the CPU: the generated HOST model against the hand-written oracle models and against finite
 differences, the language rules, and that the generated DEVICE models compile for gfx950 with hiprtc (no GPU needed for any of this)."""
+import json
 import os
 
 import numpy as np
@@ -234,28 +235,32 @@ def test_the_device_resident_kernel_families_of_the_diffsl_test_models_compile_w
         m.precompile(fe.FAMILY_RESIDENT_SDIRK)  # TR-BDF2 / ESDIRK34 of a DAE stay on the wavefront-per-member kernels
 
 
-REF_SPM = "/root/reference/book/src/primer/src/spm.ds"
 REF_DFN = "/root/reference/crates/diffsol/benches/pybamm_dfn.diffsl"
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SPM), reason="the reference checkout is only present in the build container")
 def test_the_references_own_spm_ds_goes_through_the_front_end_and_equals_the_built_in_model(O, fe):
-    """book/src/primer/src/spm.ds read from the reference checkout at test time (not copied): same dimensions, structure, initial state, right-hand side,
-    J v and stop conditions as the built-in single-particle model, which was written from the same file."""
-    code = open(REF_SPM).read()
+    """book/src/primer/src/spm.ds of the reference, as recorded through this front end (tests/golden/reference_spm_ds.json, written by
+    tests/golden/make_reference_spm_ds.py; the file's text is not copied): same dimensions, structure, initial state, right-hand side, J v and stop
+    conditions as the built-in single-particle model, which was written from the same file — and as this repository's DiffSL text of the model."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_spm_ds.json")) as f:
+        rec = json.load(f)
+    rd = rec["dims"]
+    assert (rd["n"], rd["nparams"], rd["nroots"], rd["nout"], rd["has_mass"], tuple(rd["band"])) == (42, 1, 2, 1, False, (1, 1, 0, 0)) and rec["defaults"] == [1.0]
+    code = D.spm(20, voltage=True)
     src, dims, defaults = fe.generate(code, fe.TARGET_HOST_C)
     assert (dims["n"], dims["nparams"], dims["nroots"], dims["nout"], dims["has_mass"], dims["band"]) == (42, 1, 2, 1, False, (1, 1, 0, 0)) and defaults.tolist() == [1.0]
     mid, ref = D.host_model(O, code), ORACLE_MODEL["spm"]
-    rng = np.random.default_rng(4)
-    for _ in range(4):
-        x = np.concatenate([rng.uniform(0, 1, 2), rng.uniform(0.2, 0.9, 20), rng.uniform(0.3, 0.95, 20)])
-        p, v = rng.uniform(0.6, 1.4, 1), rng.standard_normal(42)
-        a, b = O.model_rhs(mid, x, p), O.model_rhs(ref, x, p, 0.0, 20)
-        assert np.allclose(a, b, rtol=1e-12, atol=1e-12 * np.abs(b).max())  # the file's Laplacian literals differ from the formula by <= 2 ulp
-        a, b = O.model_jac_mul(mid, x, p, v), O.model_jac_mul(ref, x, p, v, 0.0, 20)
-        assert np.allclose(a, b, rtol=1e-12, atol=1e-12 * np.abs(b).max())
-        assert np.allclose(O.model_root(mid, x, p), O.model_root(ref, x, p, 0.0, 20), rtol=1e-12)
-    assert np.array_equal(O.model_init(mid, [1.0]), O.model_init(ref, [1.0], 0.0, 20))
+    assert len(rec["points"]) == 4
+    for pt in rec["points"]:
+        x, p, v = np.array(pt["x"]), np.array(pt["p"]), np.array(pt["v"])
+        for got, b in ((np.array(pt["rhs"]), O.model_rhs(ref, x, p, 0.0, 20)), (O.model_rhs(mid, x, p), np.array(pt["rhs"]))):
+            assert np.allclose(got, b, rtol=1e-12, atol=1e-12 * np.abs(b).max())  # the file's Laplacian literals differ from the formula by <= 2 ulp
+        for got, b in ((np.array(pt["jac_mul"]), O.model_jac_mul(ref, x, p, v, 0.0, 20)), (O.model_jac_mul(mid, x, p, v), np.array(pt["jac_mul"]))):
+            assert np.allclose(got, b, rtol=1e-12, atol=1e-12 * np.abs(b).max())
+        assert np.allclose(pt["root"], O.model_root(ref, x, p, 0.0, 20), rtol=1e-12)
+        assert np.allclose(O.model_root(mid, x, p), pt["root"], rtol=1e-12)
+    assert np.array_equal(rec["init"], O.model_init(ref, rec["init_inputs"], 0.0, 20))
+    assert np.array_equal(O.model_init(mid, rec["init_inputs"]), rec["init"])
 
 
 @pytest.mark.skipif(not os.path.exists(REF_DFN), reason="the reference checkout is only present in the build container")

@@ -1,0 +1,280 @@
+// Device-resident explicit Runge-Kutta integrator, Tsit45 (launch code and documentation: dsh_erk_resident.hip).  In a header so that run-time-compiled model
+// modules (dsh_jit.hip) instantiate the same kernel for user models.
+#pragma once
+#include "dsh_resident.hpp"
+
+namespace dsh {
+
+constexpr int kErkStages = 7, kErkPoly = 4, kErkOrder = 4;
+
+// Tableau::tsit45 (crates/diffsol/src/ode_solver/tableau.rs:161-304).  The numbers below are data of the method; tests/test_erk_ref_golden.py parses the lines between
+// the two markers and compares them with tests/golden/reference_tsit45.json.  The first column of `a` is not typed in: the reference computes it as
+// a(i,0) = c(i) - (a(i,1) + ... + a(i,i-1)), summed left to right from zero (tableau.rs:221-227), and so does erk_a() below.
+// TSIT45-TABLEAU-BEGIN
+constexpr double kTsitC[7] = {0.0, 0.161, 0.327, 0.9, 0.9800255409045097, 1.0, 1.0};
+constexpr double kTsitB[7] = {0.09646076681806523, 0.01, 0.4798896504144996, 1.379008574103742, -3.290069515436081, 2.324710524099774, 0.0};
+constexpr double kTsitD[7] = {-0.001780011052225777, -0.0008164344596567469, 0.007880878010261995, -0.1447110071732629, 0.5823571654525552, -0.45808210592918697, 0.015151515151515152};
+// a(i,j) for 1 <= j < i <= 5, row by row: a21 | a31 a32 | a41 a42 a43 | a51 a52 a53 a54
+constexpr double kTsitALower[10] = {0.335480655492357, -6.359448489975075, 4.362295432869581, -11.74888356406283, 7.495539342889836, -0.09249506636175525, -12.92096931784711, 8.159367898576159, -0.071584973281401, -0.02826905039406838};
+// dense output: b_i(theta) = sum_q beta[q][i] theta^(q+1)
+constexpr double kTsitBeta[4][7] = {
+    {1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0},
+    {-2.76370619727483, 0.1317, 3.93029623689475, -12.4110771669337, 37.509313416511, -27.8965262891973, 1.5},
+    {2.91325546182191, -0.2234, -5.9410338721315, 30.3381886302823, -88.1789048947664, 65.0918946747937, -4.0},
+    {-1.05308849772902, 0.1017, 2.49062728565125, -16.5481028892449, 47.3795219628193, -34.8706578614966, 2.5}};
+// TSIT45-TABLEAU-END
+
+// a(i, j), i = 1..6, j < i (row 6 = b: first same as last)
+__host__ __device__ constexpr double erk_a(int i, int j) {
+  if (i == 6) return kTsitB[j];
+  const int row0 = (i - 2) * (i - 1) / 2;  // kTsitALower offset of row i (i >= 2)
+  if (j >= 1) return kTsitALower[row0 + j - 1];
+  double a_sum = 0.0;
+  for (int q = 1; q < i; ++q) a_sum += kTsitALower[row0 + q - 1];
+  return kTsitC[i] - a_sum;
+}
+
+struct ErkConsts {
+  ResidentConsts r;
+  // ExplicitRkConfig (config.rs:132-160): the four step-size bounds of Rk::factor
+  double min_shrink, max_shrink, min_growth, max_growth;
+  // OdeSolverMethod::solve (method.rs:227-258 over :881-961): steps_cap > 0 makes the launch write the state after EVERY accepted step (y_out [steps_cap][N][nb],
+  // steps_t_out [steps_cap][nb]; columns beyond steps_cap are counted, not stored) instead of interpolating at save points
+  double* steps_t_out;
+  int steps_cap, steps_pad;
+};
+
+// One lane per member: ExplicitRk::step (explicit_rk.rs:196-243) over the Rk core (runge_kutta.rs), root finding on the dense output, tstop, solve_dense /
+// solve.  Per lane: the 7 stage increments (diff, 7 x N), state and old state (y, dy, old_y), the error vector and the controller's scalars — no LDS.
+// The register allocator picks the occupancy (no waves-per-SIMD attribute): see DESIGN.md for the compiler's numbers.
+template <class Mdl, bool BA, bool WAVE>
+__global__ __launch_bounds__(64) void k_erk_resident(int64_t nb, const double* __restrict__ p_g, const double* __restrict__ atol_g, const ErkConsts* __restrict__ Cp,
+                                                     const double* __restrict__ t_eval, double* __restrict__ y_out, int32_t* __restrict__ stats_out,
+                                                     int32_t* __restrict__ status_out, double* __restrict__ t_root_out, int32_t* __restrict__ root_idx_out,
+                                                     int32_t* __restrict__ ncols_out, unsigned long long* __restrict__ totals) {
+  constexpr int N = Mdl::N, NP = Mdl::NP, NR = Mdl::NROOTS > 0 ? Mdl::NROOTS : 1, S = kErkStages;
+  static_assert(!Mdl::HAS_MASS, "explicit Runge-Kutta methods take no mass matrix (MassMatrixNotSupported, runge_kutta.rs:236-239)");
+  const ErkConsts& T = *Cp;
+  const ResidentConsts& C = T.r;
+  const dsh_adaptive_options& o = C.o;
+  const int64_t bglobal = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  const bool active = bglobal < nb;  // the other lanes shadow the wavefront's first member (no stores): invisible in the group reductions
+  const int64_t b = active ? bglobal : (int64_t)blockIdx.x * 64;
+  const double rtol = C.rtol;
+  double p[NP], atol[N];
+  load_vec<NP>(p_g, nb, b, p);
+DSH_UNROLL_N
+  for (int i = 0; i < N; ++i) atol[i] = BA ? atol_g[i] : atol_g[(int64_t)i * nb + b];
+
+  // ------------------------------------------------------------ RkState::new_and_consistent(problem, tableau.order())
+  int32_t status = kRsOk;
+  double t = C.t0, h = 0.0;
+  double y[N], dy[N];
+  Mdl::init(t, p, y);
+  Mdl::rhs(t, y, p, dy);
+  const bool det = o.deterministic_pow != 0;
+  h = initial_step_size<Mdl, WAVE>(t, C.h0, y, dy, p, atol, rtol, kErkOrder, det);
+
+  // ------------------------------------------------------------ Rk::_new (runge_kutta.rs:107-194)
+  double diff[S][N];
+#pragma unroll
+  for (int j = 0; j < S; ++j)
+DSH_UNROLL_N
+    for (int i = 0; i < N; ++i) diff[j][i] = 0.0;
+  double old_y[N], old_t = t;  // old_state (its dy and h are never read)
+DSH_UNROLL_N
+  for (int i = 0; i < N; ++i) old_y[i] = y[i];
+  double g0[NR] = {0.0};
+  double rf_t0 = t;
+  if constexpr (Mdl::NROOTS > 0) Mdl::root(t, y, p, g0);
+  bool has_prev_err = false;
+  double prev_err = 0.0;
+  int n_steps = 0, n_err_fails = 0;
+
+  // handle_tstop (runge_kutta.rs:752-781): 0 nothing, 1 reached, 2 StopTimeBeforeCurrentTime
+  bool has_tstop = true;
+  const double tstop = t_eval[C.n_eval - 1];
+  auto handle_tstop = [&]() __attribute__((always_inline)) -> int {
+    const double troundoff = 100.0 * kEps * (fabs(t) + fabs(h));
+    if (fabs(t - tstop) <= troundoff) return 1;
+    if ((h > 0.0 && tstop < t - troundoff) || (h < 0.0 && tstop > t + troundoff)) return 2;
+    if ((h > 0.0 && t + h > tstop + troundoff) || (h < 0.0 && t + h < tstop - troundoff)) {
+      const double factor = (tstop - t) / h;
+      h *= factor;
+    }
+    return 0;
+  };
+  // interpolate_inplace (runge_kutta.rs:1080-1127) inside the last step [old_t, t]: interpolate_beta_function (:968-981) + interpolate_from_diff (:962-966)
+  auto interpolate = [&](double tt, double (&ret)[N]) __attribute__((always_inline)) {
+    const double dt = t - old_t;
+    const double theta = dt == 0.0 ? 1.0 : (tt - old_t) / dt;
+    double thetav[kErkPoly];
+    thetav[0] = theta;
+#pragma unroll
+    for (int q = 1; q < kErkPoly; ++q) thetav[q] = theta * thetav[q - 1];
+    double bf[S];
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+      double acc = 1.0 * kTsitBeta[0][i] * thetav[0];
+#pragma unroll
+      for (int q = 1; q < kErkPoly; ++q) acc = 1.0 * kTsitBeta[q][i] * thetav[q] + acc;
+      bf[i] = acc;
+    }
+DSH_UNROLL_N
+    for (int i = 0; i < N; ++i) {
+      double acc = 1.0 * diff[0][i] * bf[0] + 1.0 * old_y[i];
+#pragma unroll
+      for (int j = 1; j < S; ++j) acc = 1.0 * diff[j][i] * bf[j] + acc;
+      ret[i] = acc;
+    }
+  };
+
+  int col = 0;
+  double t_root = 0.0;
+  int root_idx = -1;
+  const bool steps_mode = T.steps_cap > 0;  // every accepted step out (ErkConsts::steps_cap)
+  auto steps_write = [&](double tw, const double (&yw)[N]) __attribute__((always_inline)) {
+    if (col < T.steps_cap && active) {
+      T.steps_t_out[(int64_t)col * nb + b] = tw;
+DSH_UNROLL_N
+      for (int i = 0; i < N; ++i) y_out[((int64_t)col * N + i) * nb + b] = yw[i];
+    }
+    col++;
+  };
+  if (steps_mode) steps_write(t, y);  // write_out before the first step (method.rs:900)
+  {  // set_stop_time (runge_kutta.rs:436-444); t_eval[0] >= t0 is checked on the host
+    const int r = handle_tstop();
+    if (r == 1) status = kRsStopTimeAtCurrentTime;
+    else if (r == 2) status = kRsStopTimeBeforeCurrentTime;
+  }
+
+  long guard = 0;
+  bool done = status != kRsOk || (!WAVE && !active);
+  while (!done) {
+    if (++guard > o.max_steps) { status = kRsMaxStepsExceeded; break; }
+    // ================================================================ ExplicitRk::step (explicit_rk.rs:196-243)
+    double hh = h;  // rk.start_step() (the state is never mutated between steps here)
+    int nattempts = 0;
+    double fac = 1.0, error_norm = 0.0;
+    double sy[N], sdy[N];  // old_state.y / old_state.dy: the stage point and its derivative
+    while (true) {
+      // start_step_attempt (runge_kutta.rs:505-516): first same as last
+DSH_UNROLL_N
+      for (int r = 0; r < N; ++r) diff[0][r] = hh * dy[r];
+#pragma unroll
+      for (int i = 1; i < S; ++i) {
+        // do_stage (runge_kutta.rs:537-566): old_state.y = y + diff[:, 0..i] a_row_i (nalgebra gemv order), diff[:, i] = h f(old_state.y, t + c_i h)
+        const double ts = t + kTsitC[i] * hh;
+DSH_UNROLL_N
+        for (int r = 0; r < N; ++r) {
+          double acc = 1.0 * diff[0][r] * erk_a(i, 0) + 1.0 * y[r];
+#pragma unroll
+          for (int j = 1; j < i; ++j) acc = 1.0 * diff[j][r] * erk_a(i, j) + acc;
+          sy[r] = acc;
+        }
+        Mdl::rhs(ts, sy, p, sdy);
+DSH_UNROLL_N
+        for (int r = 0; r < N; ++r) diff[i][r] = hh * sdy[r];
+      }
+      // error_norm (runge_kutta.rs:783-800): diff d, no linear solve
+      double err[N];
+DSH_UNROLL_N
+      for (int r = 0; r < N; ++r) {
+        double acc = 1.0 * diff[0][r] * kTsitD[0];
+#pragma unroll
+        for (int j = 1; j < S; ++j) acc = 1.0 * diff[j][r] * kTsitD[j] + acc;
+        err[r] = acc;
+      }
+      error_norm = fmax(0.0, group_norm<WAVE>(wms<N>(err, y, atol, rtol)));
+      {  // Rk::factor (runge_kutta.rs:466-495) with safety_factor = 1
+        const double safety = 0.9 * 1.0;
+        double f = safety * pi_controller_raw(error_norm, has_prev_err, prev_err, o.pi_control_integral, o.pi_control_proportional, kErkOrder + 1, det);
+        if (f > T.max_shrink && f < T.min_growth) f = 1.0;
+        if (f < T.min_shrink) f = T.min_shrink;
+        if (f > T.max_growth) f = T.max_growth;
+        fac = f;
+      }
+      if (error_norm < 1.0) break;
+      hh *= fac;
+      nattempts += 1;
+      has_prev_err = false;
+      n_err_fails += 1;  // error_test_fail (runge_kutta.rs:843-867)
+      if (nattempts >= o.max_error_test_failures) { status = kRsTooManyErrorTestFailures; break; }
+      if (fabs(hh) < o.min_timestep) { status = kRsStepSizeTooSmall; break; }
+    }
+    if (status != kRsOk) break;
+    prev_err = error_norm; has_prev_err = true;
+    // ---- step_accepted(h, h * factor, rescale_dy = false) (runge_kutta.rs:894-960): old_state <- (last stage point, its derivative, t + h, new_h); swap
+    {
+DSH_UNROLL_N
+      for (int r = 0; r < N; ++r) { old_y[r] = y[r]; y[r] = sy[r]; dy[r] = sdy[r]; }
+      const double nt = t + hh;
+      old_t = t;
+      t = nt;
+      h = hh * fac;
+    }
+    n_steps += 1;
+    int reason = 0;  // 0 internal, 1 tstop, 3 root
+    if constexpr (Mdl::NROOTS > 0) {
+      const int rr = check_root<Mdl, WAVE>(g0, rf_t0, y, t, p, interpolate, t_root, root_idx);
+      if (rr == 2) { status = kRsRootBatchMismatch; break; }
+      if (rr == 1) reason = 3;
+    }
+    if (reason == 0 && has_tstop) {
+      const int r = handle_tstop();
+      if (r == 2) { status = kRsStopTimeBeforeCurrentTime; break; }
+      if (r == 1) { has_tstop = false; reason = 1; }
+    }
+    // ================================================================ solve_dense (method.rs:467-520) / solve (:881-961)
+    const double upto = reason == 3 ? t_root : t;
+    if (steps_mode) {  // InternalTimestep / TstopReached -> write_out: state.y; a root is written below, at the root
+      if (reason != 3) steps_write(t, y);
+    } else
+    while (col < C.n_eval && t_eval[col] <= upto) {
+      double yv[N];
+      interpolate(t_eval[col], yv);
+DSH_UNROLL_N
+      for (int i = 0; i < N; ++i) if (active) y_out[((int64_t)col * N + i) * nb + b] = yv[i];
+      col++;
+    }
+    if (reason == 3) {  // state_mut_back(t_root): the column after the drained ones holds the state at the root
+      double yv[N];
+      interpolate(t_root, yv);
+      if (steps_mode) steps_write(t_root, yv);
+      else if (col < C.n_eval) {
+DSH_UNROLL_N
+        for (int i = 0; i < N; ++i) if (active) y_out[((int64_t)col * N + i) * nb + b] = yv[i];
+        col++;
+      }
+      done = true;
+    }
+    if (reason == 1) done = true;
+  }
+  if (active) {
+    if (ncols_out != nullptr) ncols_out[b] = col;
+    if (!steps_mode)
+    for (; col < C.n_eval; ++col) {  // columns that were never reached (root stop or error exit): NaN
+DSH_UNROLL_N
+      for (int i = 0; i < N; ++i) y_out[((int64_t)col * N + i) * nb + b] = __builtin_nan("");
+    }
+    if (status_out != nullptr) status_out[b] = status;
+    if (t_root_out != nullptr) t_root_out[b] = root_idx >= 0 ? t_root : __builtin_nan("");
+    if (root_idx_out != nullptr) root_idx_out[b] = root_idx;
+    if (stats_out != nullptr) {  // the SDIRK layout: steps, Newton iterations, LU setups, error-test failures, Newton failures — an explicit method has no Newton, no LU
+      stats_out[0 * nb + b] = n_steps;
+      stats_out[1 * nb + b] = 0;
+      stats_out[2 * nb + b] = 0;
+      stats_out[3 * nb + b] = n_err_fails;
+      stats_out[4 * nb + b] = 0;
+    }
+  }
+  const unsigned long long mine[6] = {active ? (unsigned long long)n_steps : 0ull, 0ull, 0ull, active ? (unsigned long long)n_err_fails : 0ull, 0ull,
+                                      (active && status != kRsOk) ? 1ull : 0ull};
+#pragma unroll
+  for (int q = 0; q < 6; ++q) {
+    const unsigned long long sum = wave_sum_u64(mine[q]);
+    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(&totals[q], sum);
+  }
+}
+
+}  // namespace dsh

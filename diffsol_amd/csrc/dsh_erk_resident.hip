@@ -1,0 +1,145 @@
+// Device-resident explicit Runge-Kutta integration — Tsit45, the reference's fourth integrator (problem.tsit45(), crates/diffsol/src/ode_solver/explicit_rk.rs) —
+// for ensembles of small NON-STIFF systems (gfx950).
+//
+// One launch integrates the whole ensemble, one lane per member, everything of ExplicitRk::step (explicit_rk.rs:196-243) and of the Rk core it calls
+// (runge_kutta.rs: start_step :446, start_step_attempt :505, do_stage :537, error_norm :783, factor :466 with the four ExplicitRkConfig bounds, error_test_fail :843,
+// step_accepted :894, handle_tstop :752, the beta-polynomial dense output :962-1002, pi_controller_raw :1313) per lane: no Jacobian, no LU, no Newton, no LDS.
+// First same as last: stage 0 is state.dy, 6 right-hand sides per attempt.  With per-member control (group = 1) every member has its own h and stops at ITS OWN event
+// time; with wavefront lock-step (group = 64) the reference's batched semantics hold per 64-member group (norms max-reduced over the wavefront, one h).
+//
+// Arithmetic is the checker's operation for operation (tests/erk_ref/erk_ref.cpp over the oracle's vector operations); compiled without contraction.  There is no
+// fast-arithmetic twin: deterministic_pow = 2 runs this kernel with the portable pow, like 1.
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "dsh_internal.hpp"
+#include "dsh_resident.hpp"
+
+#include "dsh_erk_kernel.hpp"
+#include "dsh_jit.hpp"
+
+using namespace dsh;
+
+namespace dsh {
+// dsh_model_has_resident(3, ..): static models without a mass matrix and without a reset operator — built-in with n <= 4, run-time-compiled (DiffSL) in the static
+// form with n <= 8 (the kernel holds 7 n stage values per lane: n = 8 still fits the register file)
+int erk_model_has_resident(int model, int64_t size) {
+  if (is_jit_model(model)) {
+    const JitInfo* ji = jit_info(model);
+    if (!ji) return 0;
+    return (ji->form == DSH_JIT_FORM_STATIC && ji->n <= 8 && !ji->has_mass && !ji->has_reset) ? 1 : 0;
+  }
+  bool ok = false;
+  dispatch_static_model(model, size, [&](auto mdl) {
+    using Mdl = decltype(mdl);
+    ok = Mdl::N <= 4 && !Mdl::HAS_MASS && !model_has_reset<Mdl>::value;
+  });
+  return ok ? 1 : 0;
+}
+}  // namespace dsh
+
+namespace {
+struct ErkStepsSpec { double* t_out; int64_t cap; };
+
+// why a model is refused, in the caller's words
+int erk_refuse(int model, int64_t size) {
+  int64_t n = 0, np = 0, nroots = 0;
+  int has_mass = 0;
+  if (dsh_model_info(model, size, &n, &np, &has_mass, &nroots) == DSH_OK && has_mass) {
+    set_error("dsh_erk_solve_resident: MassMatrixNotSupported — explicit Runge-Kutta methods take no mass matrix (the reference refuses it too); use BDF, TR-BDF2 or ESDIRK34 "
+              "(dsh_bdf_solve_adaptive, dsh_sdirk_solve_resident)");
+    return DSH_E_UNSUPPORTED;
+  }
+  set_error("dsh_erk_solve_resident: Tsit45 runs register-resident only — built-in static models with n <= 4, DiffSL models in the static form with n <= 8, no reset operator; "
+            "banded lane-per-member, wavefront-per-member and workgroup-per-member forms (n > 8) are not provided: use BDF, TR-BDF2 or ESDIRK34 for this model");
+  return DSH_E_UNSUPPORTED;
+}
+
+int erk_solve_resident_impl(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol, double t0,
+                            double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double* y_out, int32_t* stats, int32_t* status,
+                            double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host, const ErkStepsSpec* steps) {
+  DSH_REQUIRE(ctx != nullptr, "ctx is null");
+  DSH_REQUIRE(method == 3, "method must be 3 (Tsit45)");
+  DSH_REQUIRE(n_eval >= 1 && t_eval_host != nullptr, "t_eval must hold at least one time");
+  DSH_REQUIRE(atol_nb == 1 || atol_nb == nb, "atol must be broadcast (nbatch 1) or per member");
+  for (int64_t q = 0; q + 1 < n_eval; ++q) DSH_REQUIRE(t_eval_host[q] <= t_eval_host[q + 1], "t_eval must be increasing (InvalidTEval)");
+  DSH_REQUIRE(t_eval_host[0] >= t0, "t_eval[0] before t0 (InvalidTEval)");
+  if (!erk_model_has_resident(model, size)) return erk_refuse(model, size);
+  if (nb == 0) return DSH_OK;
+  ErkConsts T;
+  std::memset((void*)&T, 0, sizeof T);
+  T.r.rtol = rtol; T.r.t0 = t0; T.r.h0 = h0; T.r.n_eval = (int)n_eval; T.r.member_lanes = 0;
+  if (opts) T.r.o = *opts; else dsh_adaptive_default_options(&T.r.o);
+  if (T.r.o.max_steps <= 0) T.r.o.max_steps = 10000000;
+  DSH_REQUIRE(T.r.o.group == 1 || T.r.o.group == 64, "group must be 1 (per member) or 64 (wavefront lock-step)");
+  // ExplicitRkConfig::default() (config.rs:141-160): NOT the BDF / SDIRK bounds dsh_adaptive_options carries
+  T.min_shrink = 0.5; T.max_shrink = 1.0; T.min_growth = 1.0; T.max_growth = 2.0;
+  if (steps) { T.steps_t_out = steps->t_out; T.steps_cap = (int)steps->cap; }
+  double* t_eval_dev = nullptr;
+  unsigned long long* totals_dev = nullptr;
+  ErkConsts* consts_dev = nullptr;
+  int rc = dsh_malloc(ctx, (int64_t)sizeof(ErkConsts), 0, (void**)&consts_dev);
+  if (rc != DSH_OK) return rc;
+  DSH_HIP_CHECK(hipMemcpyAsync(consts_dev, &T, sizeof(ErkConsts), hipMemcpyHostToDevice, ctx->stream));
+  rc = dsh_malloc(ctx, (int64_t)(sizeof(double) * n_eval), 0, (void**)&t_eval_dev);
+  if (rc != DSH_OK) return rc;
+  rc = dsh_malloc(ctx, (int64_t)(sizeof(unsigned long long) * 8), 1, (void**)&totals_dev);
+  if (rc != DSH_OK) return rc;
+  DSH_HIP_CHECK(hipMemcpyAsync(t_eval_dev, t_eval_host, sizeof(double) * n_eval, hipMemcpyHostToDevice, ctx->stream));
+  const bool ba = atol_nb == 1 && nb != 1;
+  const bool wave = T.r.o.group == 64;
+  const dim3 grid((unsigned)((nb + 63) / 64)), blk(64);  // 64 members per wavefront in both modes
+  DSH_HIP_CHECK(timing_begin(ctx));
+  if (is_jit_model(model)) {
+    const std::string name = std::string("dsh::k_erk_resident<dsh::JitModel, ") + (ba ? "true" : "false") + ", " + (wave ? "true" : "false") + ">";
+    rc = jit_launch(ctx, model, "dsh_erk_kernel.hpp", name, {name}, name, grid, blk, 0, nb, p, atol, (const ErkConsts*)consts_dev, (const double*)t_eval_dev, y_out, stats,
+                    status, t_root, root_idx, ncols, totals_dev);
+    if (rc != DSH_OK) return rc;
+  } else
+  dispatch_static_model(model, size, [&](auto mdl) {
+    using Mdl = decltype(mdl);
+    if constexpr (Mdl::N <= 4 && !Mdl::HAS_MASS && !model_has_reset<Mdl>::value) {
+#define DSH_ERK_LAUNCH(BA, WAVE)                                                                                                                        \
+  hipLaunchKernelGGL((k_erk_resident<Mdl, BA, WAVE>), grid, blk, 0, ctx->stream, nb, p, atol, (const ErkConsts*)consts_dev, (const double*)t_eval_dev, \
+                     y_out, stats, status, t_root, root_idx, ncols, totals_dev)
+      if (ba) { if (wave) DSH_ERK_LAUNCH(true, true); else DSH_ERK_LAUNCH(true, false); }
+      else { if (wave) DSH_ERK_LAUNCH(false, true); else DSH_ERK_LAUNCH(false, false); }
+#undef DSH_ERK_LAUNCH
+    }
+  });
+  DSH_HIP_CHECK(hipGetLastError());
+  DSH_HIP_CHECK(timing_end(ctx));
+  unsigned long long totals[8] = {0};
+  DSH_HIP_CHECK(hipMemcpyAsync(totals, totals_dev, sizeof(unsigned long long) * 6, hipMemcpyDeviceToHost, ctx->stream));
+  DSH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  DSH_HIP_CHECK(timing_collect(ctx));
+  dsh_free(ctx, t_eval_dev);
+  dsh_free(ctx, totals_dev);
+  dsh_free(ctx, consts_dev);
+  if (totals_host) for (int q = 0; q < 6; ++q) totals_host[q] = (int64_t)totals[q];
+  return DSH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int dsh_erk_solve_resident(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol, double t0,
+                           double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double* y_out, int32_t* stats, int32_t* status,
+                           double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host) {
+  DSH_ENTER(ctx);
+  return erk_solve_resident_impl(ctx, method, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, t_eval_host, n_eval, y_out, stats, status, t_root, root_idx, ncols,
+                                 totals_host, nullptr);
+}
+// OdeSolverMethod::solve (method.rs:227-258 over :881-961) inside the launch: the state after every accepted step of every member (arguments as
+// dsh_sdirk_solve_resident_steps)
+int dsh_erk_solve_resident_steps(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol,
+                                 double t0, double h0, const dsh_adaptive_options* opts, double t_final, int64_t max_cols, double* y_out, double* t_out, int32_t* stats,
+                                 int32_t* status, double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host) {
+  DSH_ENTER(ctx);
+  DSH_REQUIRE(max_cols >= 2 && max_cols <= 0x7fffffff && y_out != nullptr && t_out != nullptr && ncols != nullptr, "dsh_erk_solve_resident_steps: max_cols >= 2, y_out, t_out and ncols are needed");
+  const ErkStepsSpec st{t_out, max_cols};
+  return erk_solve_resident_impl(ctx, method, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, &t_final, 1, y_out, stats, status, t_root, root_idx, ncols, totals_host, &st);
+}
+
+}  // extern "C"

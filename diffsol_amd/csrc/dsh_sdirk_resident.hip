@@ -26,12 +26,14 @@ namespace dsh {
 bool sdirk_fast_launch(int method, int model, int64_t size, bool ba, bool wave, dim3 grid, hipStream_t stream, int64_t nb, const double* p, const double* atol,
                        const SdirkConsts* consts, const double* t_eval, double* y_out, int32_t* stats, int32_t* status, double* t_root, int32_t* root_idx, int32_t* ncols,
                        unsigned long long* totals);  // dsh_sdirk_fast.hip
+int erk_model_has_resident(int model, int64_t size);  // dsh_erk_resident.hip
 }
 
 extern "C" {
 
 int dsh_model_has_resident(int method, int model, int64_t size) {
   if (method == 0) return dsh_model_has_adaptive(model, size);
+  if (method == 3) return erk_model_has_resident(model, size);  // Tsit45
   if (method != 1 && method != 2) return 0;
   if (is_jit_model(model)) {
     const JitInfo* ji = jit_info(model);

@@ -11,6 +11,7 @@
 
 #include "bdf.hpp"
 #include "diffsl.hpp"
+#include "explicit_rk.hpp"
 #include "sdirk.hpp"
 
 using namespace diffsol_hip;
@@ -39,6 +40,15 @@ struct dshs_solver {
       auto k = std::make_unique<Sdirk>(problem, method == DSHS_METHOD_TR_BDF2 ? Tableau::tr_bdf2() : Tableau::esdirk34());
       fused = k->is_fused();
       sdirk = k.get();
+      solver = std::move(k);
+    } else if (method == DSHS_METHOD_TSIT45) {
+      // problem.tsit45(): device-resident only (explicit_rk.hpp); refused here like the reference refuses at construction (check_explicit_rk)
+      auto k = std::make_unique<ExplicitRkDeviceOnly>(problem);
+      int m = 0; int64_t sz = 0;
+      if (!problem.eqn->registry_model(&m, &sz) || !dsh_model_has_resident(3, m, sz))
+        throw LaError(DSH_E_UNSUPPORTED, "Tsit45 runs register-resident only — built-in static models with n <= 4, DiffSL models in the static form with n <= 8, no reset operator; "
+                                         "banded lane-per-member, wavefront-per-member and workgroup-per-member forms (n > 8) are not provided: use BDF, TR-BDF2 or ESDIRK34 for this model");
+      fused = false;
       solver = std::move(k);
     } else {
       throw LaError(DSH_E_INVALID, "unknown method");
@@ -104,6 +114,12 @@ ResidentPick pick_resident(const dshs_solver* s, int group, bool for_auto = fals
   ResidentPick r;
   r.method = s->method == DSHS_METHOD_BDF ? 0 : (s->method == DSHS_METHOD_TR_BDF2 ? 1 : 2);
   if (group != 1 && group != 64) return r;
+  if (s->method == DSHS_METHOD_TSIT45) {  // one form only: the register-resident explicit kernel (dsh_erk_solve_resident); make_solver() checked the model
+    int m = 0; int64_t sz = 0;
+    r.method = 3;
+    if (!s->problem.sens && s->problem.eqn->registry_model(&m, &sz) && dsh_model_has_resident(3, m, sz)) { r.ok = true; r.model = m; r.size = sz; }
+    return r;
+  }
   if (s->problem.sens) {
     // forward sensitivities: the register-resident BDF integrates them alongside (k_bdf_adaptive<.., SENS>; static ODE models, n <= 4, no root functions) on an
     // explicit request (dshs_solve_dense_adaptive_sens); dshs_solve_dense keeps the host-driven path, whose solver state dshs_interpolate_sens reads
@@ -173,6 +189,8 @@ int resolve_mode(const dshs_solver* s) {
     }();
     mode = env_mode;
   }
+  if (mode == DSHS_ENSEMBLE_AUTO && s->method == DSHS_METHOD_TSIT45)  // no host-driven path to fall back to: per member with root functions, else wavefront groups
+    return s->problem.eqn->nroots() > 0 ? DSHS_ENSEMBLE_PER_MEMBER : DSHS_ENSEMBLE_WAVEFRONT;
   if (mode == DSHS_ENSEMBLE_AUTO) {
     // the device-resident integrators start from the problem's (t0, y0): a solver that was stepped by hand continues on the host path
     if (s->solver->get_statistics().number_of_steps != 0 || s->solver->t() != s->problem.t0) return DSHS_ENSEMBLE_LOCKSTEP;
@@ -355,6 +373,9 @@ void run_resident(dshs_solver* s, const double* t_eval, int64_t nt, int group, i
   else if (wave_member)
     rc = dsh_bdf_solve_wave_member(c, model, size, nb, params_dev, s->problem.atol.ptr(), 1, s->problem.rtol, s->problem.t0, s->problem.h0, &o,
                                    t_eval, nt, out, (int32_t*)stats_dev, (int32_t*)status_dev, (double*)troot_dev, (int32_t*)ridx_dev, (int32_t*)ncols_dev, totals);
+  else if (method == 3)
+    rc = dsh_erk_solve_resident(c, method, model, size, nb, params_dev, s->problem.atol.ptr(), 1, s->problem.rtol, s->problem.t0, s->problem.h0, &o, t_eval, nt, out,
+                                (int32_t*)stats_dev, (int32_t*)status_dev, (double*)troot_dev, (int32_t*)ridx_dev, (int32_t*)ncols_dev, totals);
   else if (method == 0)
     rc = dsh_bdf_solve_adaptive(c, model, size, nb, params_dev, s->problem.atol.ptr(), 1, s->problem.rtol, s->problem.t0, s->problem.h0, &o,
                                 t_eval, nt, out, (int32_t*)stats_dev, (int32_t*)status_dev, (double*)troot_dev, (int32_t*)ridx_dev, (int32_t*)ncols_dev, totals);
@@ -725,6 +746,7 @@ int dshs_set_ensemble_mode(dshs_solver* s, int mode) {
   return guarded([&]() {
     if (mode != DSHS_ENSEMBLE_AUTO && mode != DSHS_ENSEMBLE_LOCKSTEP && mode != DSHS_ENSEMBLE_PER_MEMBER && mode != DSHS_ENSEMBLE_WAVEFRONT)
       throw LaError(DSH_E_INVALID, "dshs_set_ensemble_mode: mode must be DSHS_ENSEMBLE_AUTO, _LOCKSTEP, _PER_MEMBER or _WAVEFRONT");
+    if (mode == DSHS_ENSEMBLE_LOCKSTEP && s->method == DSHS_METHOD_TSIT45) throw LaError(DSH_E_UNSUPPORTED, kTsit45HostDriven);
     if ((mode == DSHS_ENSEMBLE_PER_MEMBER || mode == DSHS_ENSEMBLE_WAVEFRONT) && !pick_resident(s, mode).ok)
       throw LaError(DSH_E_UNSUPPORTED, "dshs_set_ensemble_mode: no device-resident kernel for this model/method in that mode");
     s->ensemble_mode = mode;
@@ -764,8 +786,9 @@ int dshs_solve_adaptive(dshs_solver* s, double t_final, int64_t max_cols, int gr
     if (!y_host || !t_host || !ncols_host || max_cols < 2) throw LaError(DSH_E_INVALID, "dshs_solve_adaptive: y_host, t_host, ncols_host and max_cols >= 2 are needed");
     if (s->problem.sens) throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_adaptive: without forward sensitivities (dshs_solve walks the host-driven path for the rest)");
     const ResidentPick pk = pick_resident(s, group);
-    const bool sdirk = s->method != DSHS_METHOD_BDF;  // TR-BDF2 / ESDIRK34
-    if (!pk.ok || (!sdirk && !pk.wave_member && !dsh_model_has_adaptive_steps(pk.model, pk.size)))
+    const bool erk = s->method == DSHS_METHOD_TSIT45;
+    const bool sdirk = s->method != DSHS_METHOD_BDF && !erk;  // TR-BDF2 / ESDIRK34
+    if (!pk.ok || (!sdirk && !erk && !pk.wave_member && !dsh_model_has_adaptive_steps(pk.model, pk.size)))
       throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_adaptive: no device-resident integrator that writes every step for this model and method (register-resident static models, banded lane-per-member forms, "
                                        "wavefront / workgroup per member); dshs_solve returns every step of the host-driven lock-step solver");
     const int64_t n = s->problem.eqn->nstates(), nb = s->ctx.nbatch();
@@ -784,6 +807,11 @@ int dshs_solve_adaptive(dshs_solver* s, double t_final, int64_t max_cols, int gr
     if (t_root_host) check(dsh_malloc(c, (int64_t)sizeof(double) * nb, 0, &troot_dev), "solve_adaptive t_root");
     if (root_idx_host) check(dsh_malloc(c, (int64_t)sizeof(int32_t) * nb, 0, &ridx_dev), "solve_adaptive root_idx");
     int64_t tot[6] = {0};
+    if (erk)
+      check(dsh_erk_solve_resident_steps(c, pk.method, pk.model, pk.size, nb, s->problem.eqn->params().ptr(), s->problem.atol.ptr(), 1, s->problem.rtol, s->problem.t0, s->problem.h0, &o,
+                                         t_final, max_cols, (double*)y_dev, (double*)t_dev, (int32_t*)stats_dev, (int32_t*)status_dev, (double*)troot_dev, (int32_t*)ridx_dev,
+                                         (int32_t*)ncols_dev, tot), "dsh_erk_solve_resident_steps");
+    else
     if (sdirk && pk.wave_member)
       check(dsh_sdirk_solve_wave_member_steps(c, pk.model, pk.size, pk.method, nb, s->problem.eqn->params().ptr(), s->problem.atol.ptr(), 1, s->problem.rtol, s->problem.t0, s->problem.h0, &o,
                                               t_final, max_cols, (double*)y_dev, (double*)t_dev, (int32_t*)stats_dev, (int32_t*)status_dev, (double*)troot_dev, (int32_t*)ridx_dev,

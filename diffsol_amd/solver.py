@@ -1,5 +1,5 @@
 """Python handle on the host-side integrators (include/diffsol_hip_solver.h): the harness tests and bench.py drive
-`OdeBuilder ... .bdf() / .tr_bdf2() / .esdirk34()` through, mirroring the reference's user API
+`OdeBuilder ... .bdf() / .tr_bdf2() / .esdirk34() / .tsit45()` through, mirroring the reference's user API
 (crates/diffsol/src/ode_solver/builder.rs, problem.rs, method.rs)."""
 import ctypes as C
 
@@ -8,7 +8,7 @@ import numpy as np
 from . import _ffi
 from ._ffi import DiffsolHipError, DshsOptions, check, vp
 
-METHOD_BDF, METHOD_TR_BDF2, METHOD_ESDIRK34 = 0, 1, 2
+METHOD_BDF, METHOD_TR_BDF2, METHOD_ESDIRK34, METHOD_TSIT45 = 0, 1, 2, 3
 
 MODELS = {
     "exponential_decay": 0, "exponential_decay_with_algebraic": 1, "exponential_decay_with_algebraic_batched": 2, "robertson_ode": 3,
@@ -294,3 +294,4 @@ class OdeBuilder:
     def bdf(self): return Solver(self._model, self._p, method=METHOD_BDF, **self._kw)
     def tr_bdf2(self): return Solver(self._model, self._p, method=METHOD_TR_BDF2, **self._kw)
     def esdirk34(self): return Solver(self._model, self._p, method=METHOD_ESDIRK34, **self._kw)
+    def tsit45(self): return Solver(self._model, self._p, method=METHOD_TSIT45, **self._kw)  # device-resident only: solve_dense / solve_dense_adaptive / solve_adaptive

@@ -544,6 +544,19 @@ int dsh_model_has_resident(int method, int model, int64_t size);
 int dsh_sdirk_solve_resident(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol,
                              double t0, double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double* y_out, int32_t* stats,
                              int32_t* status, double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host);
+/* Device-resident Tsit45 (method 3), the explicit Runge-Kutta method of problem.tsit45(): ExplicitRk::step (ode_solver/explicit_rk.rs:196-243) + Rk core
+ * (runge_kutta.rs) + RootFinder + solve_dense per member, one launch per ensemble solve, no Jacobian / LU / Newton — for NON-STIFF sweeps.  Models
+ * (dsh_model_has_resident(3, model, size)): static models WITHOUT a mass matrix (MassMatrixNotSupported, as in the reference) and without a reset operator —
+ * built-in with n <= 4, run-time-compiled in the static form with n <= 8; every other form returns DSH_E_UNSUPPORTED.  Arguments and outputs as
+ * dsh_sdirk_solve_resident / dsh_sdirk_solve_resident_steps with method = 3; stats rows 1, 2 and 4 (Newton iterations, LU setups, Newton failures) are zero.
+ * The step-size bounds are those of ExplicitRkConfig::default() (config.rs:141-160: growth <= 2, shrink >= 0.5, no dead band) — the four
+ * *_timestep_growth / *_timestep_shrink fields of opts, which carry the BDF / SDIRK defaults, are not read.  deterministic_pow = 2 runs the exact kernel. */
+int dsh_erk_solve_resident(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol,
+                           double t0, double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double* y_out, int32_t* stats,
+                           int32_t* status, double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host);
+int dsh_erk_solve_resident_steps(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol,
+                                 double t0, double h0, const dsh_adaptive_options* opts, double t_final, int64_t max_cols, double* y_out, double* t_out, int32_t* stats,
+                                 int32_t* status, double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host);
 
 
 /* ------------------------------------------------------------------------------------------------------------------------------------------------

@@ -23,6 +23,12 @@ typedef struct dsh_ctx dsh_ctx; /* include/diffsol_hip.h */
 #define DSHS_METHOD_BDF 0      /* OdeSolverProblem::bdf       crates/diffsol/src/ode_solver/problem.rs:649-655 */
 #define DSHS_METHOD_TR_BDF2 1  /* OdeSolverProblem::tr_bdf2   problem.rs:839-861 (sdirk_solver_from_tableau!) */
 #define DSHS_METHOD_ESDIRK34 2 /* OdeSolverProblem::esdirk34 */
+/* OdeSolverProblem::tsit45 (crates/diffsol/src/ode_solver/explicit_rk.rs), the explicit method for NON-STIFF problems.  Device-resident only (dsh_erk_solve_resident,
+ * include/diffsol_hip.h): dshs_solve_dense in the ensemble modes auto / per member / wavefront, dshs_solve_dense_adaptive and dshs_solve_adaptive integrate it; the
+ * host-driven entries (dshs_step, dshs_set_stop_time, dshs_interpolate, dshs_solve, dshs_solve_to_points, DSHS_ENSEMBLE_LOCKSTEP) return DSH_E_UNSUPPORTED with a message
+ * that names the entries that work.  dshs_create refuses (DSH_E_UNSUPPORTED) a model with a mass matrix — MassMatrixNotSupported, as the reference does —, a model
+ * without a register-resident form (n > 8, run-time-sized, reset operator) and, through dshs_create_sens, forward sensitivities. */
+#define DSHS_METHOD_TSIT45 3
 
 #define DSHS_STOP_INTERNAL_TIMESTEP 0 /* OdeSolverStopReason, crates/diffsol/src/ode_solver/method.rs:22-40 */
 #define DSHS_STOP_ROOT_FOUND 1

@@ -48,6 +48,36 @@ __device__ __forceinline__ void guarded(bool c, F&& f) {
   }
 }
 
+// A value that is the same in all 64 lanes of a wavefront lock-step group, moved to scalar registers (v_readfirstlane on every 32-bit half).  The
+// compiler cannot see that such a value is uniform when it comes back from a function call (rpow is not inlined) or is carried round the step loop
+// next to one: it keeps it in vector registers, and every `if` on it becomes exec-mask bookkeeping (s_and_saveexec / s_or / s_cbranch_execz) around
+// code that all lanes enter or all skip.  After uniform<WAVE>() the same test is a compare into VCC and ONE scalar branch.  The bits do not change
+// and the floating-point arithmetic stays where it was.  Per-member control (WAVE = false): the identity.
+template <bool WAVE>
+__device__ __forceinline__ int uniform(int v) {
+  if constexpr (WAVE) return __builtin_amdgcn_readfirstlane(v);
+  else return v;
+}
+template <bool WAVE>
+__device__ __forceinline__ bool uniform(bool v) {
+  if constexpr (WAVE) return __builtin_amdgcn_readfirstlane((int)v) != 0;
+  else return v;
+}
+template <bool WAVE>
+__device__ __forceinline__ double uniform(double v) {
+  if constexpr (WAVE) return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+  else return v;
+}
+// group_norm<WAVE> (dsh_resident.hpp) for this kernel: its arguments are weighted mean squares — never negative — so the wavefront maximum takes the
+// one-pass reduction (wave_max_nonneg_f64, dsh_device.hpp: the same bits, returned in scalar registers).  That reduction reads its result from lane 63
+// and lets rows without a DPP source read +0: every call site must be reached by ALL 64 lanes of the wavefront (here the shadow lanes of a ragged last
+// group keep executing the whole kernel and only their stores are masked), and the argument must not be negative.  Not a drop-in for group_norm elsewhere.
+template <bool WAVE>
+__device__ __forceinline__ double group_norm_w(double v) {
+  if constexpr (WAVE) return wave_max_nonneg_f64(v);
+  else return v;
+}
+
 // wavefronts per SIMD the kernel is compiled for: 2 for the register-resident models (256 VGPRs hold the whole BDF state); the run-time-compiled banded
 // form, whose state lives in per-lane memory anyway, overrides it (dsh_jit.hip) to trade registers for latency hiding
 #ifndef DSH_ADAPTIVE_WAVES_PER_EU
@@ -58,7 +88,7 @@ __device__ __forceinline__ void guarded(bool c, F&& f) {
 #ifndef DSH_ADAPTIVE_DT_PRIVATE
 #define DSH_ADAPTIVE_DT_PRIVATE 0
 #endif
-// FAST (opt-in, dsh_adaptive_options::deterministic_pow == 2; instantiated only in dsh_adaptive_fast.hip, which is compiled with -ffp-contract=fast and
+// FAST (dsh_adaptive_options::deterministic_pow == 2, the default arithmetic of Solver.solve_dense; instantiated only in dsh_adaptive_fast.hip, which is compiled with -ffp-contract=fast and
 // reciprocal-math division): ocml's pow, fused multiply-adds, the Newton norm's weights as reciprocals computed once per solve.  NOT bit-comparable with the
 // oracle: held to 1e-6 relative on the states at tight tolerances (tests/test_gpu_adaptive.py).
 template <class Mdl, bool BA, bool WAVE, bool SEG = false, bool SENS = false, bool FAST = false>
@@ -93,7 +123,7 @@ DSH_UNROLL_N
     Mdl::init(t, p, y);
     Mdl::rhs(t, y, p, f0);
     if (!group_all<WAVE>(set_consistent<Mdl, WAVE>(t, p, y, f0, atol, rtol, C.r))) status = kRsInitialConditionDidNotConverge;
-    h = initial_step_size<Mdl, WAVE>(t, C.r.h0, y, f0, p, atol, rtol, 1, det);
+    h = uniform<WAVE>(initial_step_size<Mdl, WAVE>(t, C.r.h0, y, f0, p, atol, rtol, 1, det));
   } else {
 DSH_UNROLL_N
     for (int i = 0; i < N; ++i) { y[i] = 0.0; f0[i] = 0.0; }
@@ -580,13 +610,16 @@ DSH_UNROLL_N
           }
           delta_ms = acc / (double)N;
         }
-        const double norm = sqrt(group_norm<WAVE>(delta_ms));
+        const double norm = sqrt(group_norm_w<WAVE>(delta_ms));
         // Convergence::check_new_iteration (convergence.rs:68-139)
+        // WAVE: norm, rate, eta, diverged and converged are scalar-register values and the tests below are scalar branches ONLY because every input is
+        // uniform for the compiler: group_norm_w returns through v_readlane, and the two rpow results go through uniform<WAVE>().  A value that comes
+        // out of a function call or a per-lane load and is mixed in here without uniform<WAVE>() brings the exec-mask form back (profiles/wave_uniform_control.md).
         niter += 1;
         bool diverged = false;
         if (has_old) {
           // pow(x, 1.0) == x exactly: the common second iteration needs no libm call
-          const double rate = niter == 2 ? norm / old_norm : rpow(norm / old_norm, 1.0 / (double)(niter - 1), det);
+          const double rate = niter == 2 ? norm / old_norm : uniform<WAVE>(rpow(norm / old_norm, 1.0 / (double)(niter - 1), det));
           if (rate > 0.9) diverged = true;
           else if (powi_rt(rate, o.max_nonlinear_solver_iterations - niter) / (1.0 - rate) * norm > o.nonlinear_solver_tolerance) diverged = true;
           else eta = rate / (1.0 - rate);
@@ -596,7 +629,7 @@ DSH_UNROLL_N
           // after a reset eta is one of two constants (convergence.rs:36-42): their 0.8th powers come from the host (the same deterministic pow)
           if ((det || FAST) && eta == C.r.eta_reset) eta = C.eta_reset_p08;
           else if ((det || FAST) && eta == C.r.eta_reset_ts) eta = C.eta_reset_ts_p08;
-          else eta = rpow(eta, 0.8, det);
+          else eta = uniform<WAVE>(rpow(eta, 0.8, det));
         }
         const bool converged = !diverged && eta * norm < o.nonlinear_solver_tolerance;
         if (niter == 1) { has_old = true; old_norm = norm; }
@@ -651,11 +684,11 @@ DSH_UNROLL_N
                 const double term = d / (fabs(sp[i]) * rtol + atol[i]);
                 acc += term * term;
               }
-              const double norm = sqrt(group_norm<WAVE>(acc / (double)N));
+              const double norm = sqrt(group_norm_w<WAVE>(acc / (double)N));
               sn += 1;
               bool diverged = false;
               if (s_has_old) {
-                const double rate = sn == 2 ? norm / s_old_norm : rpow(norm / s_old_norm, 1.0 / (double)(sn - 1), det);
+                const double rate = sn == 2 ? norm / s_old_norm : uniform<WAVE>(rpow(norm / s_old_norm, 1.0 / (double)(sn - 1), det));
                 if (rate > 0.9) diverged = true;
                 else if (powi_rt(rate, o.max_nonlinear_solver_iterations - sn) / (1.0 - rate) * norm > o.nonlinear_solver_tolerance) diverged = true;
                 else eta = rate / (1.0 - rate);
@@ -664,7 +697,7 @@ DSH_UNROLL_N
                 if (eta < min_eta) eta = min_eta;
                 if (det && eta == C.r.eta_reset) eta = C.eta_reset_p08;
                 else if (det && eta == C.r.eta_reset_ts) eta = C.eta_reset_ts_p08;
-                else eta = rpow(eta, 0.8, det);
+                else eta = uniform<WAVE>(rpow(eta, 0.8, det));
               }
               const bool converged = !diverged && eta * norm < o.nonlinear_solver_tolerance;
               if (sn == 1) { s_has_old = true; s_old_norm = norm; }
@@ -699,10 +732,13 @@ DSH_UNROLL_N
 DSH_UNROLL_N
       for (int i = 0; i < N; ++i) ydelta[i] = x[i] - yp[i];
       // error_control (bdf.rs:812-843): norm against the CURRENT state y
-      error_norm = fmax(0.0, group_norm<WAVE>(wms_y(ydelta)) * sEc2[order - 1]);
+      // WAVE: the error test, the step-size factor with its clamps, the order-selection norms and the chosen order, h, t and the stop-time tests are scalar
+      // branches for the same reason as the convergence test: group_norm_w returns in scalar registers, and h (initial_step_size) and the error-test
+      // failure's pi_controller_raw, which end in the rpow call, go through uniform<WAVE>().  Keep it so when adding an input to any of them.
+      error_norm = fmax(0.0, group_norm_w<WAVE>(wms_y(ydelta)) * sEc2[order - 1]);
       if constexpr (SENS) {
         if (C.sens_error_control)  // bdf.rs:844-858 — error_const2[order], not [order - 1]
-          for (int j = 0; j < NP; ++j) error_norm = fmax(error_norm, group_norm<WAVE>(wms<N>(s_delta[j], s_cur[j], s_atol, C.sens_rtol)) * sEc2[order]);
+          for (int j = 0; j < NP; ++j) error_norm = fmax(error_norm, group_norm_w<WAVE>(wms<N>(s_delta[j], s_cur[j], s_atol, C.sens_rtol)) * sEc2[order]);
       }
       const double maxiter = (double)o.max_nonlinear_solver_iterations;
       safety = 0.9 * (2.0 * maxiter + 1.0) / (2.0 * maxiter + (double)niter);
@@ -777,7 +813,7 @@ DSH_UNROLL_N
         break;
       }
       // @phase error-test failure
-      double factor = safety * pi_controller_raw(error_norm, has_prev_err, prev_err, o.pi_control_integral, o.pi_control_proportional, order + 1, det);
+      double factor = safety * uniform<WAVE>(pi_controller_raw(error_norm, has_prev_err, prev_err, o.pi_control_integral, o.pi_control_proportional, order + 1, det));
       has_prev_err = false;
       if (factor < o.min_timestep_shrink) factor = o.min_timestep_shrink;
       double new_h;
@@ -821,8 +857,8 @@ DSH_UNROLL_N
       }
       }
       const double inf = __builtin_huge_val();
-      double error_m_norm = order > 1 ? group_norm<WAVE>(wms_y(col_m)) * sEc2[order - 1] : inf;
-      double error_p_norm = order < kMaxOrder ? group_norm<WAVE>(wms_y(col_p)) * sEc2[order + 1] : inf;
+      double error_m_norm = order > 1 ? group_norm_w<WAVE>(wms_y(col_m)) * sEc2[order - 1] : inf;
+      double error_p_norm = order < kMaxOrder ? group_norm_w<WAVE>(wms_y(col_p)) * sEc2[order + 1] : inf;
       if constexpr (SENS) {  // predict_error_control with the augmented system (bdf.rs:871-932): the `error_norm.max(err)` chain from zero, then the sensitivities' terms
         if (order > 1) error_m_norm = fmax(0.0, error_m_norm);
         if (order < kMaxOrder) error_p_norm = fmax(0.0, error_p_norm);
@@ -836,8 +872,8 @@ DSH_UNROLL_N
               for (int j = 1; j < kNC; ++j) { if (j == order) vm = S[q][j][i]; if (j == order + 2) vp = S[q][j][i]; }
               cm[i] = vm; cp[i] = vp;
             }
-            if (order > 1) error_m_norm = fmax(error_m_norm, group_norm<WAVE>(wms<N>(cm, s_cur[q], s_atol, C.sens_rtol)) * sEc2[order - 1]);
-            if (order < kMaxOrder) error_p_norm = fmax(error_p_norm, group_norm<WAVE>(wms<N>(cp, s_cur[q], s_atol, C.sens_rtol)) * sEc2[order + 1]);
+            if (order > 1) error_m_norm = fmax(error_m_norm, group_norm_w<WAVE>(wms<N>(cm, s_cur[q], s_atol, C.sens_rtol)) * sEc2[order - 1]);
+            if (order < kMaxOrder) error_p_norm = fmax(error_p_norm, group_norm_w<WAVE>(wms<N>(cp, s_cur[q], s_atol, C.sens_rtol)) * sEc2[order + 1]);
           }
       }
       const double pi_i = o.pi_control_integral, pi_p = o.pi_control_proportional;

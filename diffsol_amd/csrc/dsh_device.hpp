@@ -94,6 +94,30 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
   const unsigned int ml = wave_max_u32(hi == mh ? lo : 0u);
   return ((unsigned long long)mh << 32) | (unsigned long long)ml;
 }
+// maximum of a NON-NEGATIVE double (a norm, a square: +0, denormal, normal or +inf) over the wavefront in ONE pass.  On such values the order of the bit
+// patterns is the order of the numbers, so the result has the bits of wave_max_u64(d2u(v)) — in about half the instructions (wave_max_u64 reduces the
+// high words, then the low words among the lanes that hold the largest high word, and combines four row results per pass).  The four butterfly stages
+// inside a row are followed by row_bcast:15 (rows 1 and 3 take in rows 0 and 2) and row_bcast:31 (row 3 takes in row 1): lane 63 then holds the maximum and ONE v_readlane
+// per half returns it in scalar registers.  v_max_f64 drops a NaN where the bit-pattern maximum keeps it (every NaN pattern lies above +inf): a
+// wavefront that holds one takes the two-pass reduction, so the bits agree there too; the NaN test does not depend on the reduction and is off its
+// chain.  All 64 lanes must be active.
+constexpr int kDppRowBcast15 = 0x142, kDppRowBcast31 = 0x143;
+// a lane without a source (the row broadcasts: row 0, rows 0 and 1) reads +0 (bound_ctrl), the identity of this maximum; the rows a broadcast reaches
+// beyond the two named above only see values of the same wavefront again.  No previous value of the destination is kept, so no register is copied first.
+template <int CTRL>
+__device__ __forceinline__ double dpp_max_f64(double v) {
+  return __builtin_fmax(v, __hiloint2double(__builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, true), __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, true)));
+}
+__device__ __forceinline__ double wave_max_nonneg_f64(double v) {
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(v != v) != 0ull, 0)) return __longlong_as_double((long long)wave_max_u64(d2u(v)));
+  v = dpp_max_f64<kDppQuadXor1>(v);
+  v = dpp_max_f64<kDppQuadXor2>(v);
+  v = dpp_max_f64<kDppRowHalfMirror>(v);
+  v = dpp_max_f64<kDppRowMirror>(v);
+  v = dpp_max_f64<kDppRowBcast15>(v);
+  v = dpp_max_f64<kDppRowBcast31>(v);
+  return __longlong_as_double((long long)readlane_u64(d2u(v), 63));
+}
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
   v += dpp_move_u64<kDppQuadXor1>(v);
   v += dpp_move_u64<kDppQuadXor2>(v);

@@ -3,7 +3,10 @@
 //
 // This translation unit alone is compiled with -ffp-contract=fast -freciprocal-math -fapprox-func (csrc/Makefile): the same kernel source as the exact
 // variant, with multiply-adds fused, divisions by reciprocal + refinement instead of the IEEE sequence, ocml's pow, and the Newton norm's weights as
-// reciprocals.  Its results are NOT bit-comparable with the oracle (every other kernel of the library is); north_star asks for 1e-6 relative on the states,
+// reciprocals.  The two powers on the Newton chain have a fixed exponent and skip the general pow (pow_p08, root_k in dsh_adaptive_kernel.hpp): eta^0.8 as
+// eta * eta^(-1/5) from a single-precision seed and three division-free Newton steps, the convergence rate's square and cube root by sqrt and cbrt; both within
+// a few ulp of the mathematical power, both feeding decisions only, and any argument outside their domain (zero, denormal, negative, infinite, NaN) takes the
+// pow call.  The order selection, the step-size controller and the initial step size keep the general pow.  Its results are NOT bit-comparable with the oracle (every other kernel of the library is); north_star asks for 1e-6 relative on the states,
 // which the tests hold it to at tight tolerances; at the bench's full size it makes the step decisions of the exact kernel (every member's five counters equal,
 // states within 1e-9: tests/test_gpu_adaptive.py).  The bitwise test tier pins the exact kernel (tests/conftest.py).
 #include "dsh_internal.hpp"

@@ -78,6 +78,35 @@ __device__ __forceinline__ double group_norm_w(double v) {
   else return v;
 }
 
+// FAST only (dsh_adaptive_fast.hip): the two powers with a fixed exponent on the Newton chain, in place of the general pow (a call of some 220 vector
+// instructions, 150 of them FP64).  Both feed decisions only (eta * norm < tol, rate > 0.9, the divergence test), never a state, and both are within a few
+// ulp of the mathematical power, as ocml's pow is.  An argument outside the stated domain takes the rpow call these replace, so zero, denormals, negative
+// numbers, +inf and NaN (norm / old_norm can be any of them in this build) keep that call's bits.  With WAVE the arguments are wavefront-uniform: the domain
+// test is one scalar branch and the call is cold code.
+//
+// x^0.8 = x * x^(-1/5) for 2^-100 < x < 2^100 (eta lies in [1e4 eps, 9] or is a reset constant below 320; the bounds keep (float)x normal and leave the
+// single-precision seed a relative error below 4e-6 over the whole domain): the seed exp2(-0.2 log2 x) by the hardware's f32 transcendentals, then three
+// division-free Newton steps w += 0.2 w (1 - x w^5) in FP64 for the inverse fifth root.  A relative error e becomes 3 e^2: 4e-6, 5e-11, 8e-21, so the
+// last step leaves w within about 1 ulp (the rounding of its own residual and update) and the product adds half an ulp.
+__device__ __forceinline__ double pow_p08(double x) {
+  if (__builtin_expect(!(x > 0x1p-100 && x < 0x1p100), 0)) return rpow(x, 0.8, false);
+  double w = (double)__builtin_amdgcn_exp2f(-0.2f * __builtin_amdgcn_logf((float)x));
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double w2 = w * w;
+    const double w5 = w2 * w2 * w;
+    w = fma(0.2 * w, fma(-x, w5, 1.0), w);
+  }
+  return x * w;
+}
+// x^(1/k) for x positive, normal and finite: sqrt for k = 2, cbrt for k = 3 (the convergence rate of the third and fourth Newton iteration; the ratio is
+// almost always in (0, 1)).  Every other k, and every other x, is the general call with the exponent as the call site wrote it.
+__device__ __forceinline__ double root_k(double x, int k) {
+  if (__builtin_expect(!((k == 2 || k == 3) && x >= 0x1p-1022 && x <= 0x1.fffffffffffffp1023), 0)) return rpow(x, 1.0 / (double)k, false);
+  if (k == 2) return sqrt(x);
+  return cbrt(x);
+}
+
 // wavefronts per SIMD the kernel is compiled for: 2 for the register-resident models (256 VGPRs hold the whole BDF state); the run-time-compiled banded
 // form, whose state lives in per-lane memory anyway, overrides it (dsh_jit.hip) to trade registers for latency hiding
 #ifndef DSH_ADAPTIVE_WAVES_PER_EU
@@ -89,8 +118,8 @@ __device__ __forceinline__ double group_norm_w(double v) {
 #define DSH_ADAPTIVE_DT_PRIVATE 0
 #endif
 // FAST (dsh_adaptive_options::deterministic_pow == 2, the default arithmetic of Solver.solve_dense; instantiated only in dsh_adaptive_fast.hip, which is compiled with -ffp-contract=fast and
-// reciprocal-math division): ocml's pow, fused multiply-adds, the Newton norm's weights as reciprocals computed once per solve.  NOT bit-comparable with the
-// oracle: held to 1e-6 relative on the states at tight tolerances (tests/test_gpu_adaptive.py).
+// reciprocal-math division): ocml's pow (the Newton chain's two fixed-exponent powers by pow_p08 / root_k above), fused multiply-adds, the Newton norm's weights as
+// reciprocals computed once per solve.  NOT bit-comparable with the oracle: held to 1e-6 relative on the states at tight tolerances (tests/test_gpu_adaptive.py).
 template <class Mdl, bool BA, bool WAVE, bool SEG = false, bool SENS = false, bool FAST = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DSH_ADAPTIVE_WAVES_PER_EU, DSH_ADAPTIVE_WAVES_PER_EU))) void k_bdf_adaptive(int64_t nb, const double* __restrict__ p_g, const double* __restrict__ atol_g, const AdaptiveConsts* __restrict__ Cp,
                                                     const double* __restrict__ t_eval, double* __restrict__ y_out, int32_t* __restrict__ stats_out,
@@ -619,7 +648,9 @@ DSH_UNROLL_N
         bool diverged = false;
         if (has_old) {
           // pow(x, 1.0) == x exactly: the common second iteration needs no libm call
-          const double rate = niter == 2 ? norm / old_norm : uniform<WAVE>(rpow(norm / old_norm, 1.0 / (double)(niter - 1), det));
+          double rate;
+          if constexpr (FAST) rate = niter == 2 ? norm / old_norm : uniform<WAVE>(root_k(norm / old_norm, niter - 1));
+          else rate = niter == 2 ? norm / old_norm : uniform<WAVE>(rpow(norm / old_norm, 1.0 / (double)(niter - 1), det));
           if (rate > 0.9) diverged = true;
           else if (powi_rt(rate, o.max_nonlinear_solver_iterations - niter) / (1.0 - rate) * norm > o.nonlinear_solver_tolerance) diverged = true;
           else eta = rate / (1.0 - rate);
@@ -629,6 +660,7 @@ DSH_UNROLL_N
           // after a reset eta is one of two constants (convergence.rs:36-42): their 0.8th powers come from the host (the same deterministic pow)
           if ((det || FAST) && eta == C.r.eta_reset) eta = C.eta_reset_p08;
           else if ((det || FAST) && eta == C.r.eta_reset_ts) eta = C.eta_reset_ts_p08;
+          else if constexpr (FAST) eta = uniform<WAVE>(pow_p08(eta));
           else eta = uniform<WAVE>(rpow(eta, 0.8, det));
         }
         const bool converged = !diverged && eta * norm < o.nonlinear_solver_tolerance;
@@ -688,7 +720,9 @@ DSH_UNROLL_N
               sn += 1;
               bool diverged = false;
               if (s_has_old) {
-                const double rate = sn == 2 ? norm / s_old_norm : uniform<WAVE>(rpow(norm / s_old_norm, 1.0 / (double)(sn - 1), det));
+                double rate;
+                if constexpr (FAST) rate = sn == 2 ? norm / s_old_norm : uniform<WAVE>(root_k(norm / s_old_norm, sn - 1));
+                else rate = sn == 2 ? norm / s_old_norm : uniform<WAVE>(rpow(norm / s_old_norm, 1.0 / (double)(sn - 1), det));
                 if (rate > 0.9) diverged = true;
                 else if (powi_rt(rate, o.max_nonlinear_solver_iterations - sn) / (1.0 - rate) * norm > o.nonlinear_solver_tolerance) diverged = true;
                 else eta = rate / (1.0 - rate);
@@ -697,6 +731,7 @@ DSH_UNROLL_N
                 if (eta < min_eta) eta = min_eta;
                 if (det && eta == C.r.eta_reset) eta = C.eta_reset_p08;
                 else if (det && eta == C.r.eta_reset_ts) eta = C.eta_reset_ts_p08;
+                else if constexpr (FAST) eta = uniform<WAVE>(pow_p08(eta));
                 else eta = uniform<WAVE>(rpow(eta, 0.8, det));
               }
               const bool converged = !diverged && eta * norm < o.nonlinear_solver_tolerance;

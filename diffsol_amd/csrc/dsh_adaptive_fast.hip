@@ -6,27 +6,53 @@
 // reciprocals.  The two powers on the Newton chain have a fixed exponent and skip the general pow (pow_p08, root_k in dsh_adaptive_kernel.hpp): eta^0.8 as
 // eta * eta^(-1/5) from a single-precision seed and three division-free Newton steps, the convergence rate's square and cube root by sqrt and cbrt; both within
 // a few ulp of the mathematical power, both feeding decisions only, and any argument outside their domain (zero, denormal, negative, infinite, NaN) takes the
-// pow call.  The order selection, the step-size controller and the initial step size keep the general pow.  Its results are NOT bit-comparable with the oracle (every other kernel of the library is); north_star asks for 1e-6 relative on the states,
+// pow call.  In lock-step groups with the default controller constants the order selection's three values x^(-1/(2k)) come from inv_root_2k_group (a single-precision
+// seed, two division-free Newton steps; at most 2.1 units of 2^-53 off, the derived bound; they feed the step size); per-member control, the error-test failure's pi_controller_raw and the initial
+// step size keep the general pow.
+//
+// Lock-step groups whose options are the defaults take k_bdf_adaptive<.., FAST, DEFOPT = true>: the options the kernel body reads are compile-time constants there
+// (DSH_ADAPTIVE_BODY_OPTIONS, dsh_adaptive_kernel.hpp: the one list behind dsh_adaptive_default_options(), the kernel's constant view and body_options_are_default
+// below), so that no option is loaded on the per-step chain.  Bit for bit the general fast kernel's results (profiles/default_options_kernel.md).  This is the instantiation bench.py times.
+//
+// Its results are NOT bit-comparable with the oracle (every other kernel of the library is); north_star asks for 1e-6 relative on the states,
 // which the tests hold it to at tight tolerances; at the bench's full size it makes the step decisions of the exact kernel (every member's five counters equal,
 // states within 1e-9: tests/test_gpu_adaptive.py).  The bitwise test tier pins the exact kernel (tests/conftest.py).
+#include <cstring>
+
 #include "dsh_internal.hpp"
 #include "dsh_resident.hpp"
 #include "dsh_adaptive_kernel.hpp"
 
 namespace dsh {
 
-bool adaptive_fast_launch(int model, int64_t size, bool ba, bool wave, dim3 grid, hipStream_t stream, int64_t nb, const double* p, const double* atol,
-                          const AdaptiveConsts* consts, const double* t_eval, double* y_out, int32_t* stats, int32_t* status, double* t_root, int32_t* root_idx,
-                          int32_t* ncols, unsigned long long* totals) {
+// Does every option the kernel body reads (DSH_ADAPTIVE_BODY_OPTIONS) hold its default, bit for bit?  -0.0 for 0.0 is not the default.
+static bool body_options_are_default(const dsh_adaptive_options& o) {
+  bool same = true;
+#define DSH_X(T, name, value) { const T dflt = value; same = same && std::memcmp(&o.name, &dflt, sizeof(T)) == 0; }
+  DSH_ADAPTIVE_BODY_OPTIONS(DSH_X)
+#undef DSH_X
+  return same;
+}
+
+// opts: the options as the launch's AdaptiveConsts hold them (host copy).  Lock-step groups whose body options are all defaults take the default-options
+// instantiation; every other call the general fast kernel, which reads them from *consts.
+bool adaptive_fast_launch(int model, int64_t size, bool ba, bool wave, const dsh_adaptive_options& opts, dim3 grid, hipStream_t stream, int64_t nb, const double* p,
+                          const double* atol, const AdaptiveConsts* consts, const double* t_eval, double* y_out, int32_t* stats, int32_t* status, double* t_root,
+                          int32_t* root_idx, int32_t* ncols, unsigned long long* totals) {
   const dim3 blk(64);
   bool launched = false;
+  const bool defopt = wave && opts.group == 64 && body_options_are_default(opts);
   dispatch_static_model(model, size, [&](auto mdl) {
     using Mdl = decltype(mdl);
     if constexpr (Mdl::N <= 4) {
 #define DSH_FAST_LAUNCH(BA, WAVE) \
   hipLaunchKernelGGL((k_bdf_adaptive<Mdl, BA, WAVE, false, false, true>), grid, blk, 0, stream, nb, p, atol, consts, t_eval, y_out, stats, status, t_root, root_idx, ncols, totals)
-      if (wave) { if (ba) DSH_FAST_LAUNCH(true, true); else DSH_FAST_LAUNCH(false, true); }
+#define DSH_FAST_DEFOPT_LAUNCH(BA) \
+  hipLaunchKernelGGL((k_bdf_adaptive<Mdl, BA, true, false, false, true, true>), grid, blk, 0, stream, nb, p, atol, consts, t_eval, y_out, stats, status, t_root, root_idx, ncols, totals)
+      if (defopt) { if (ba) DSH_FAST_DEFOPT_LAUNCH(true); else DSH_FAST_DEFOPT_LAUNCH(false); }
+      else if (wave) { if (ba) DSH_FAST_LAUNCH(true, true); else DSH_FAST_LAUNCH(false, true); }
       else { if (ba) DSH_FAST_LAUNCH(true, false); else DSH_FAST_LAUNCH(false, false); }
+#undef DSH_FAST_DEFOPT_LAUNCH
 #undef DSH_FAST_LAUNCH
       launched = true;
     }

@@ -36,6 +36,38 @@ struct AdaptiveConsts {
 };
 constexpr int kSegDbl = 128, kSegInt = 32;  // slots per member (upper bounds for n <= 4)
 
+// The solver options the BODY of k_bdf_adaptive reads through `o`, each with the value dsh_adaptive_default_options() gives it: the ONE list behind that function
+// (dsh_adaptive.hip), behind the compile-time view of the default-options instantiation (AdaptiveDefaultOptions below; k_bdf_adaptive<.., DEFOPT = true>) and behind
+// the host test that decides whether a call may take that instantiation (adaptive_fast_launch, dsh_adaptive_fast.hip).  Not in the list, because the body never reads
+// them: the ic_* fields (set_consistent reads them through C.r), deterministic_pow and group (they choose the kernel).  A field the body starts to read belongs here.
+#define DSH_ADAPTIVE_BODY_OPTIONS(X)             \
+  X(int, max_nonlinear_solver_iterations, 10)    \
+  X(int, max_error_test_failures, 40)            \
+  X(int, max_nonlinear_solver_failures, 50)      \
+  X(double, nonlinear_solver_tolerance, 0.2)     \
+  X(double, min_timestep, 1e-13)                 \
+  X(double, max_timestep_growth, 2.0)            \
+  X(double, min_timestep_growth, 2.0)            \
+  X(double, max_timestep_shrink, 0.9)            \
+  X(double, min_timestep_shrink, 0.5)            \
+  X(int, update_jacobian_after_steps, 20)        \
+  X(int, update_rhs_jacobian_after_steps, 50)    \
+  X(double, threshold_to_update_jacobian, 0.3)   \
+  X(double, threshold_to_update_rhs_jacobian, 0.2) \
+  X(double, pi_control_proportional, 0.0)        \
+  X(double, pi_control_integral, 0.5)            \
+  X(int64_t, max_steps, 10000000)
+// `o` of the default-options instantiation: every field a constant the compiler folds, nothing read from memory.  Constructed from the options in memory, which it
+// ignores, so that the kernel declares `o` in one line for both forms.
+struct AdaptiveDefaultOptions {
+  __host__ __device__ constexpr AdaptiveDefaultOptions(const dsh_adaptive_options&) {}
+#define DSH_X(T, name, value) static constexpr T name = value;
+  DSH_ADAPTIVE_BODY_OPTIONS(DSH_X)
+#undef DSH_X
+};
+template <bool DEFOPT> struct adaptive_options_view { using type = const dsh_adaptive_options&; };
+template <> struct adaptive_options_view<true> { using type = const AdaptiveDefaultOptions; };
+
 // `if (c) body` that STAYS a branch.  In wavefront lock-step groups the BDF order is wavefront-uniform (a scalar register), and the loops over the
 // difference columns test it per column: the compiler turns such tiny guarded blocks into selects (v_cndmask on every 32-bit half: 56 % of the
 // kernel's VALU instructions were not FP64, profiles/r02) although a scalar branch would skip them for nothing.  An empty volatile asm inside the block
@@ -107,6 +139,56 @@ __device__ __forceinline__ double root_k(double x, int k) {
   return cbrt(x);
 }
 
+// a^b for b >= 0 by the multiplications of powi_rt (dsh_resident.hpp), in its order: the same bits.  powi_rt also forms 1 / r for a negative exponent and selects it
+// away; the exponent of the convergence-rate test, max_nonlinear_solver_iterations - niter, is never negative, which the compiler cannot see.
+__device__ __forceinline__ double powi_nonneg(double a, int b) {
+  unsigned u = (unsigned)b;
+  double r = 1.0;
+  while (true) {
+    if (u & 1u) r *= a;
+    u >>= 1;
+    if (u == 0u) break;
+    a *= a;
+  }
+  return r;
+}
+template <bool FAST>
+__device__ __forceinline__ double powi_rate(double a, int b) {
+  if constexpr (FAST) return powi_nonneg(a, b);
+  else return powi_rt(a, b);
+}
+
+// FAST only, lock-step groups: the step-size controller's power with the default controller constants (pi_control_proportional == 0, pi_control_integral == 0.5),
+// x^(-1/(2k)) with k = order, order + 1, order + 2 in 1..7, in place of the general pow.  Unlike the two helpers above these values feed the new step size.
+// For 2^-100 < x < 2^100: the seed exp2(-log2((float)x) / 2k) by the f32 transcendentals (relative error below 1e-5: the logarithm's absolute error, 1e-5 at
+// |log2 x| = 100, is halved at least), then kInvRootSteps division-free Newton steps w += (w / 2k) (1 - x w^2k) in FP64; an error e becomes (2k + 1) / 2 e^2, at most
+// 7.5 e^2: 1e-5, 7.5e-10, 4e-18.  w^2k = (w^k)^2, w^k by squaring with a per-lane select on each bit of k.
+constexpr int kInvRootSteps = 2;
+__device__ __forceinline__ bool inv_root_2k_domain(double x, int k) { return (x > 0x1p-100) & (x < 0x1p100) & (k >= 1) & (k <= 7); }
+__device__ __forceinline__ double inv_root_2k(double x, int k) {
+  const float n_f = (float)(2 * k);
+  const double c = 1.0 / (double)(2 * k);
+  double w = (double)__builtin_amdgcn_exp2f(-__builtin_amdgcn_logf((float)x) * __builtin_amdgcn_rcpf(n_f));
+#pragma unroll
+  for (int i = 0; i < kInvRootSteps; ++i) {
+    const double w2 = w * w, w4 = w2 * w2;
+    double pk = (k & 1) ? w : 1.0;
+    pk *= (k & 2) ? w2 : 1.0;
+    pk *= (k & 4) ? w4 : 1.0;
+    w = fma(w * c, fma(-x, pk * pk, 1.0), w);
+  }
+  return w;
+}
+// The call site's form: every lane of the wavefront brings (x, k) and the exponent `expo` its pow call would take, -(0.5 / k) as the controller writes it.  +inf (the
+// order neighbour that does not exist at order 1 or kMaxOrder) gives +0 as pow(+inf, negative) does.  ANY other argument outside the domain in any lane — zero, a
+// denormal, a negative number, NaN, beyond the bounds, k outside 1..7 — and the whole wavefront makes that pow call: one ballot, one scalar branch, the call is cold code.
+__device__ __forceinline__ double inv_root_2k_group(double x, int k, double expo) {
+  const bool is_inf = x == __builtin_huge_val();
+  if (__builtin_expect(!__all(is_inf | inv_root_2k_domain(x, k)), 0)) return rpow(x, expo, false);
+  const double w = inv_root_2k(is_inf ? 1.0 : x, k);  // every lane computes: a select, not an exec-mask region
+  return is_inf ? 0.0 : w;
+}
+
 // wavefronts per SIMD the kernel is compiled for: 2 for the register-resident models (256 VGPRs hold the whole BDF state); the run-time-compiled banded
 // form, whose state lives in per-lane memory anyway, overrides it (dsh_jit.hip) to trade registers for latency hiding
 #ifndef DSH_ADAPTIVE_WAVES_PER_EU
@@ -120,7 +202,9 @@ __device__ __forceinline__ double root_k(double x, int k) {
 // FAST (dsh_adaptive_options::deterministic_pow == 2, the default arithmetic of Solver.solve_dense; instantiated only in dsh_adaptive_fast.hip, which is compiled with -ffp-contract=fast and
 // reciprocal-math division): ocml's pow (the Newton chain's two fixed-exponent powers by pow_p08 / root_k above), fused multiply-adds, the Newton norm's weights as
 // reciprocals computed once per solve.  NOT bit-comparable with the oracle: held to 1e-6 relative on the states at tight tolerances (tests/test_gpu_adaptive.py).
-template <class Mdl, bool BA, bool WAVE, bool SEG = false, bool SENS = false, bool FAST = false>
+// DEFOPT (k_bdf_adaptive<.., FAST = true, DEFOPT = true>; instantiated only in dsh_adaptive_fast.hip, for lock-step groups): every option the body reads through `o` is
+// the constant of DSH_ADAPTIVE_BODY_OPTIONS instead of a load from *Cp inside the step loop (the other launch constants are still read where they are used); launched only when the caller's options equal those constants bit for bit.
+template <class Mdl, bool BA, bool WAVE, bool SEG = false, bool SENS = false, bool FAST = false, bool DEFOPT = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DSH_ADAPTIVE_WAVES_PER_EU, DSH_ADAPTIVE_WAVES_PER_EU))) void k_bdf_adaptive(int64_t nb, const double* __restrict__ p_g, const double* __restrict__ atol_g, const AdaptiveConsts* __restrict__ Cp,
                                                     const double* __restrict__ t_eval, double* __restrict__ y_out, int32_t* __restrict__ stats_out,
                                                     int32_t* __restrict__ status_out, double* __restrict__ t_root_out, int32_t* __restrict__ root_idx_out,
@@ -136,8 +220,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DSH_ADAPTIVE
   if constexpr (SEG) { if (C.seg_lane_member != nullptr) b_ = C.seg_lane_member[b_]; }  // segmented runs: the member this lane works for in this launch
   const int64_t b = b_;
   const bool fresh = !SEG || C.seg_fresh != 0;  // not a resumed launch
-  const dsh_adaptive_options& o = C.r.o;
-  const bool det = !FAST && o.deterministic_pow != 0;
+  typename adaptive_options_view<DEFOPT>::type o = C.r.o;
+  const bool det = !FAST && C.r.o.deterministic_pow != 0;
   const double rtol = C.r.rtol;
   double p[NP], atol[N];
   load_vec<NP>(p_g, nb, b, p);
@@ -652,7 +736,7 @@ DSH_UNROLL_N
           if constexpr (FAST) rate = niter == 2 ? norm / old_norm : uniform<WAVE>(root_k(norm / old_norm, niter - 1));
           else rate = niter == 2 ? norm / old_norm : uniform<WAVE>(rpow(norm / old_norm, 1.0 / (double)(niter - 1), det));
           if (rate > 0.9) diverged = true;
-          else if (powi_rt(rate, o.max_nonlinear_solver_iterations - niter) / (1.0 - rate) * norm > o.nonlinear_solver_tolerance) diverged = true;
+          else if (powi_rate<FAST>(rate, o.max_nonlinear_solver_iterations - niter) / (1.0 - rate) * norm > o.nonlinear_solver_tolerance) diverged = true;
           else eta = rate / (1.0 - rate);
         } else {
           const double min_eta = 1e4 * 2.220446049250313e-16;
@@ -724,7 +808,7 @@ DSH_UNROLL_N
                 if constexpr (FAST) rate = sn == 2 ? norm / s_old_norm : uniform<WAVE>(root_k(norm / s_old_norm, sn - 1));
                 else rate = sn == 2 ? norm / s_old_norm : uniform<WAVE>(rpow(norm / s_old_norm, 1.0 / (double)(sn - 1), det));
                 if (rate > 0.9) diverged = true;
-                else if (powi_rt(rate, o.max_nonlinear_solver_iterations - sn) / (1.0 - rate) * norm > o.nonlinear_solver_tolerance) diverged = true;
+                else if (powi_rate<FAST>(rate, o.max_nonlinear_solver_iterations - sn) / (1.0 - rate) * norm > o.nonlinear_solver_tolerance) diverged = true;
                 else eta = rate / (1.0 - rate);
               } else {
                 const double min_eta = 1e4 * 2.220446049250313e-16;
@@ -924,7 +1008,12 @@ DSH_UNROLL_N
         const double errs = which == 0 ? error_m_norm : (which == 1 ? error_norm : error_p_norm);
         const double base = (l6 & 1) ? prev_err : errs;
         const double expo = (l6 & 1) ? kp : (two ? -(ki + kp) : -ki);
-        const double r = rpow(l6 < 6 ? base : 1.0, expo, det);
+        // FAST with the default controller constants: lanes 0, 2 and 4 take x^(-1/(2k)) from inv_root_2k_group (no pow call unless an argument is outside its domain);
+        // the test is a scalar branch on two scalar registers, or folded (DEFOPT).  ONE conditional expression with nothing of the first arm ahead of it: without FAST only
+        // the second arm is compiled, and the exact kernels come out instruction for instruction as they were (profiles/default_options_kernel.md, section 2).
+        const double r = (FAST && pi_p == 0.0 && pi_i == 0.5)
+                             ? inv_root_2k_group((l6 < 6 && !(l6 & 1)) ? errs : 1.0, (l6 < 6 && !(l6 & 1)) ? order + which : 1, -ki)
+                             : rpow(l6 < 6 ? base : 1.0, expo, det);
         auto rl = [&](int lane) __attribute__((always_inline)) -> double {
           return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(r), lane), __builtin_amdgcn_readlane(__double2loint(r), lane));
         };

@@ -56,6 +56,10 @@ DEVICE_ABI = {
     "dsh_ctx_set_poll": (cint, [vp, cint]),
     "dsh_ctx_get_timing": (cint, [vp, c_i64p, c_dp]),
     "dsh_ctx_get_timing_overhead": (cint, [vp, c_dp, c_dp]),
+    "dsh_ctx_set_op_queue": (cint, [vp, cint]),
+    "dsh_ctx_get_op_queue": (cint, [vp]),
+    "dsh_ctx_flush": (cint, [vp]),
+    "dsh_ctx_op_queue_stats": (cint, [vp, C.POINTER(C.c_int64)]),
     "dsh_malloc": (cint, [vp, i64, cint, C.POINTER(vp)]),
     "dsh_free": (cint, [vp, vp]),
     "dsh_memset_zero": (cint, [vp, vp, i64]),
@@ -212,6 +216,8 @@ HOST_ABI = {
     "dshs_reset": (cint, [vp]),
     "dshs_context": (vp, [vp]),
     "dshs_set_linear_solve_mode": (cint, [vp, cint]),
+    "dshs_set_op_queue": (cint, [vp, cint]),
+    "dshs_get_op_queue_stats": (cint, [vp, C.POINTER(C.c_int64)]),
     "dshs_set_kernel_timing": (cint, [vp, cint]),
     "dshs_set_kernel_timing_target": (cint, [vp, cint]),
     "dshs_get_kernel_timing": (cint, [vp, c_i64p, c_dp]),

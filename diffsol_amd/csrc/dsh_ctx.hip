@@ -171,6 +171,11 @@ int dsh_ctx_create(int device, void* stream, dsh_ctx** out) {
     const bool multi = ws && std::atoi(ws) > 1;
     ctx->poll = env ? std::string(env) != "sync" : !multi;
   }
+  {
+    // initial mode of the op queue (dsh_ctx_set_op_queue; default off): DSH_OP_QUEUE=1 runs an unchanged program under it
+    const char* env = std::getenv("DSH_OP_QUEUE");
+    ctx->opq_on = env && *env && std::atoi(env) != 0;
+  }
   *out = ctx;
   return DSH_OK;
 }
@@ -178,6 +183,7 @@ int dsh_ctx_create(int device, void* stream, dsh_ctx** out) {
 void dsh_ctx_destroy(dsh_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
+  (void)opq_flush(ctx, kOpqFlushEntry);  // queued ops write memory the caller may have handed to someone else's stream: they run before the context goes
   (void)hipStreamSynchronize(ctx->stream);
   if (ctx->pool) { for (auto& kv : *ctx->pool) (void)hipFree(kv.second); delete ctx->pool; }
   if (ctx->live) { for (auto& kv : *ctx->live) (void)hipFree(kv.first); delete ctx->live; }
@@ -206,7 +212,11 @@ int dsh_ctx_sync(dsh_ctx* ctx) {
   DSH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return DSH_OK;
 }
-void* dsh_ctx_stream(dsh_ctx* ctx) { return (void*)ctx->stream; }
+// a caller that asks for the stream is about to put work of its own on it: the queued ops go first
+void* dsh_ctx_stream(dsh_ctx* ctx) {
+  ::dsh::ctx_guard guard(ctx);
+  return (void*)ctx->stream;
+}
 int dsh_ctx_device(dsh_ctx* ctx) { return ctx->device; }
 int dsh_ctx_set_block(dsh_ctx* ctx, int threads) {
   DSH_ENTER(ctx);
@@ -277,8 +287,10 @@ int dsh_ctx_get_timing(dsh_ctx* ctx, int64_t* launches, double* total_ms) {
   return DSH_OK;
 }
 
+// Op queue: handing a block from the pool to an owner (and back) is host bookkeeping — the queue keeps the order of the calls, so a queued op of the old owner still
+// runs before anything the new owner does — and does not flush.  What touches the stream does: the zeroing memset, a real hipFree, the out-of-memory sweep.
 int dsh_malloc(dsh_ctx* ctx, int64_t nbytes, int zero, void** out) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
   DSH_REQUIRE(nbytes >= 0 && out, "bad arguments");
   const size_t want = nbytes > 0 ? (size_t)nbytes : 8;
   void* p = nullptr;
@@ -294,6 +306,7 @@ int dsh_malloc(dsh_ctx* ctx, int64_t nbytes, int zero, void** out) {
       // out of memory with blocks still parked (a sweep over ensemble sizes leaves dead sizes behind — the cache only reuses exact matches): give every parked
       // block back to the runtime and try once more.  The parked blocks may still be read by work in flight, hence the synchronise.
       (void)hipGetLastError();
+      { const int rc = opq_flush(ctx, kOpqFlushEntry); if (rc != DSH_OK) return rc; }
       DSH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
       for (auto& kv : *ctx->pool) (void)hipFree(kv.second);
       ctx->pool->clear();
@@ -307,15 +320,21 @@ int dsh_malloc(dsh_ctx* ctx, int64_t nbytes, int zero, void** out) {
     }
   }
   (*ctx->live)[p] = want;
-  if (zero && nbytes > 0) DSH_HIP_CHECK(hipMemsetAsync(p, 0, (size_t)nbytes, ctx->stream));
+  if (zero && nbytes > 0) {
+    // the memset must not overtake queued users of a recycled block
+    const int rc = opq_flush(ctx, kOpqFlushEntry);
+    if (rc != DSH_OK) { ctx->live->erase(p); ctx->pool->emplace(want, p); ctx->pool_bytes += want; return rc; }
+    DSH_HIP_CHECK(hipMemsetAsync(p, 0, (size_t)nbytes, ctx->stream));
+  }
   *out = p;
   return DSH_OK;
 }
 int dsh_free(dsh_ctx* ctx, void* p) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
   if (!p) return DSH_OK;
   auto it = ctx->live->find(p);
   if (it == ctx->live->end()) {  // not ours (or already freed): fall back to the runtime
+    { const int rc = opq_flush(ctx, kOpqFlushEntry); if (rc != DSH_OK) return rc; }
     DSH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     DSH_HIP_CHECK(hipFree(p));
     return DSH_OK;
@@ -323,6 +342,7 @@ int dsh_free(dsh_ctx* ctx, void* p) {
   const size_t sz = it->second;
   ctx->live->erase(it);
   if (ctx->pool_bytes + sz > ctx->pool_limit) {  // a quarter of the device's memory (72 GB of the 288 GB of an MI355X) may stay parked per context
+    { const int rc = opq_flush(ctx, kOpqFlushEntry); if (rc != DSH_OK) return rc; }
     DSH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     DSH_HIP_CHECK(hipFree(p));
     return DSH_OK;
@@ -351,8 +371,15 @@ int dsh_d2h(dsh_ctx* ctx, void* dst, const void* src, int64_t nbytes) {
   return DSH_OK;
 }
 int dsh_d2d(dsh_ctx* ctx, void* dst, const void* src, int64_t nbytes) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
   if (nbytes <= 0) return DSH_OK;
+  if (ctx->opq_on && ((uintptr_t)dst | (uintptr_t)src | (uintptr_t)nbytes) % 8 == 0) {
+    // a copy of whole doubles is an op of the queue.  A raw copy has no batch size and no broadcast operand: it joins a chain of the same length under that chain's
+    const int64_t total = nbytes / 8;
+    const int64_t nb = ctx->opq.count > 0 && ctx->opq.total == total ? ctx->opq.nb : 1;
+    return opq_enqueue(ctx, opq::OP_COPY, total / nb, nb, (double*)dst, nullptr, (const double*)src, nb, nullptr, nb, 0.0, 0.0);
+  }
+  { const int rc = opq_flush(ctx, kOpqFlushEntry); if (rc != DSH_OK) return rc; }
   DSH_HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)nbytes, hipMemcpyDeviceToDevice, ctx->stream));
   return DSH_OK;
 }

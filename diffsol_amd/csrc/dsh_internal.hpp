@@ -11,6 +11,7 @@
 
 #include "../../include/diffsol_hip.h"
 #include "dsh_device.hpp"
+#include "dsh_opq_plan.hpp"
 
 namespace dsh {
 
@@ -97,6 +98,12 @@ struct dsh_ctx {
   // constants + save points of the last device-resident solve, kept on the device between solves (dsh_adaptive.hip); freed by dsh_ctx_destroy
   unsigned char* const_cache_dev = nullptr;
   std::vector<unsigned char>* const_cache_host = nullptr;
+  // Deferred element-wise op queue (dsh_opq.hip, dsh_ctx_set_op_queue; off by default).  While it is on, the element-wise entry points append to `opq` instead of
+  // launching, and the chain is launched as ONE k_op_chain by the next entry point that is not one of them (DSH_ENTER flushes) or by a hazard / a full chain.
+  // INVARIANT: while opq.count > 0 nothing is put on `stream` and `stream` is not waited on.
+  bool opq_on = false;
+  dsh::opq::Chain opq;
+  int64_t opq_stats[4] = {0, 0, 0, 0};  // ops enqueued, chain launches, flushes forced by a hazard or a full chain, flushes forced by a non-queuing call
 };
 
 struct dsh_lu {
@@ -134,21 +141,37 @@ extern "C" __attribute__((visibility("hidden"))) int lu_ensure_storage(dsh_lu* l
 
 namespace dsh {
 
+// launch the queued chain of a context, if any (dsh_opq.hip); `why`: the counter the flush is booked under
+enum { kOpqFlushHazard = 2, kOpqFlushEntry = 3, kOpqFlushExplicit = -1 };
+int opq_flush(dsh_ctx* ctx, int why);
+// record dst (and dst2) = op(a, b, s0, s1) over n * nb elements (operand nbatch 1 with nb != 1: broadcast); launches the chain first when the planner says so.
+// Only called while ctx->opq_on, under the context lock, after the entry point has validated its arguments.
+int opq_enqueue(dsh_ctx* ctx, int32_t op, int64_t n, int64_t nb, double* dst, double* dst2, const double* a, int64_t anb, const double* b, int64_t bnb, double s0,
+                double s1);
+
 // Scope guard of an entry point: takes the context's lock and, when the calling thread is not the one that used the context last, binds this thread's current HIP
 // device to the context's (what dsh_ctx_bind_thread did on request; a context re-created at the same address on another thread is covered too).
 struct ctx_guard {
   dsh_ctx* c;
-  explicit ctx_guard(const dsh_ctx* cc) : c(const_cast<dsh_ctx*>(cc)) {
+  int rc = DSH_OK;  // of the flush
+  // flush: launch the chain the op queue holds before the entry point puts anything on the stream or waits for it; only the entry points that themselves enqueue
+  // (and host bookkeeping that never touches the stream) pass false
+  explicit ctx_guard(const dsh_ctx* cc, bool flush = true) : c(const_cast<dsh_ctx*>(cc)) {
     if (!c) return;
     c->mu.lock();
     const std::thread::id me = std::this_thread::get_id();
     if (c->last_thread != me) { (void)hipSetDevice(c->device); c->last_thread = me; }
+    if (flush && c->opq.count > 0) rc = opq_flush(c, kOpqFlushEntry);
   }
   ~ctx_guard() { if (c) c->mu.unlock(); }
   ctx_guard(const ctx_guard&) = delete;
   ctx_guard& operator=(const ctx_guard&) = delete;
 };
-#define DSH_ENTER(ctxptr) ::dsh::ctx_guard _dsh_ctx_guard(ctxptr)
+#define DSH_ENTER(ctxptr)                       \
+  ::dsh::ctx_guard _dsh_ctx_guard(ctxptr);      \
+  if (_dsh_ctx_guard.rc != DSH_OK) return _dsh_ctx_guard.rc
+// the same for the entry points that enqueue into the op queue: no flush
+#define DSH_ENTER_QUEUE(ctxptr) ::dsh::ctx_guard _dsh_ctx_guard(ctxptr, false)
 
 // Start a reducing launch of `nblocks` workgroups: makes sure the record buffer is large enough and returns the device pointer the
 // kernel writes to plus the sequence tag it must stamp.

@@ -170,6 +170,7 @@ __attribute__((visibility("hidden"))) int lu_ensure_storage(dsh_lu* lu) {
 }
 void dsh_lu_destroy(dsh_lu* lu) {
   if (!lu) return;
+  ::dsh::ctx_guard guard(lu->ctx);  // launches what the op queue holds: nothing stays queued across a wait on the stream
   (void)hipStreamSynchronize(lu->ctx->stream);
   (void)dsh_free(lu->ctx, lu->factors);
   (void)dsh_free(lu->ctx, lu->pivots);

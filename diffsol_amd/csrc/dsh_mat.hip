@@ -4,6 +4,7 @@
 // The matrices on the hot path are tiny per system (n x 8 difference array, (k+1)^2 R*U, n x s stage matrix), so "GEMM" here is
 // a per-lane dot product streamed from HBM — bandwidth-bound, deliberately not an MFMA kernel.
 #include "dsh_internal.hpp"
+#include "dsh_ew_ops.hpp"
 
 using namespace dsh;
 
@@ -39,7 +40,7 @@ __global__ void k_scale_add_assign(int64_t total, int64_t nb, double* __restrict
                                    const double* __restrict__ y) {
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
     double xv = x[BX ? idx / nb : idx], yv = y[BY ? idx / nb : idx];
-    self[idx] = yv * beta + xv;
+    self[idx] = dsh::ew::FScaleAdd{beta}(xv, yv);
   }
 }
 // the same on the band |i - j| <= (kl below, ku above) of n x n matrices only: thread (d, i, b) handles entry (i, i + d - kl) — the entries outside the
@@ -90,7 +91,7 @@ __global__ void k_set_data_with_indices(int64_t nidx, int64_t nb, double* __rest
 // column i += alpha*column j  (value = self[k,i] + alpha*self[k,j])
 __global__ void k_column_axpy(int64_t total, double* __restrict__ ci, const double* __restrict__ cj, double alpha) {
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x)
-    ci[idx] = ci[idx] + alpha * cj[idx];
+    ci[idx] = dsh::ew::FColumnAxpy{alpha}(ci[idx], cj[idx]);
 }
 
 // y = alpha*A*x + beta*y with nalgebra's accumulation order: first column carries beta (beta==0 never reads y),
@@ -169,14 +170,15 @@ int dsh_mat_get_diagonal(dsh_ctx* ctx, int64_t n, int64_t nb, const double* mat,
   return DSH_OK;
 }
 int dsh_mat_set_column(dsh_ctx* ctx, int64_t nrows, int64_t ncols, int64_t nb, double* mat, int64_t j, const double* v, int64_t vnb) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
   DSH_REQUIRE(j >= 0 && j < ncols, "column index out of bounds");
   return dsh_vec_copy(ctx, nrows, nb, v, vnb, mat + j * nrows * nb);
 }
 int dsh_mat_scale_add_assign(dsh_ctx* ctx, int64_t nelem, int64_t nb, double* self, const double* x, int64_t xnb, double beta, const double* y,
                              int64_t ynb) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
   DSH_CHECK_NB(xnb, nb); DSH_CHECK_NB(ynb, nb);
+  if (ctx->opq_on) return opq_enqueue(ctx, opq::OP_SCALE_ADD, nelem, nb, self, nullptr, x, xnb, y, ynb, beta, 0.0);
   int64_t total = nelem * nb;
   if (total == 0) return DSH_OK;
   bool bx = xnb == 1 && nb != 1, by = ynb == 1 && nb != 1;
@@ -214,11 +216,12 @@ int dsh_mat_set_data_with_indices(dsh_ctx* ctx, int64_t nelem_self, int64_t nele
   return DSH_OK;
 }
 int dsh_mat_column_axpy(dsh_ctx* ctx, int64_t nrows, int64_t nb, double* mat, double alpha, int64_t j, int64_t i) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
   DSH_REQUIRE(i != j, "column index cannot be the same");
   DSH_REQUIRE(i >= 0 && j >= 0, "column index out of bounds");
   int64_t total = nrows * nb;
   if (total == 0) return DSH_OK;
+  if (ctx->opq_on) return opq_enqueue(ctx, opq::OP_COLUMN_AXPY, nrows, nb, mat + i * total, nullptr, mat + i * total, nb, mat + j * total, nb, alpha, 0.0);
   hipLaunchKernelGGL(k_column_axpy, ew_grid(total), dim3(kBlock), 0, ctx->stream, total, mat + i * total, (const double*)(mat + j * total), alpha);
   DSH_HIP_CHECK(hipGetLastError());
   return DSH_OK;

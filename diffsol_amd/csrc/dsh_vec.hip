@@ -7,6 +7,7 @@
 // results are bit-identical to the oracle.
 #include <cstdlib>
 #include "dsh_internal.hpp"
+#include "dsh_ew_ops.hpp"
 
 using namespace dsh;
 
@@ -50,15 +51,8 @@ __global__ void k_generate(int64_t total, double* __restrict__ dst, F f) {
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) dst[idx] = f(idx);
 }
 
-struct FAdd { __device__ double operator()(double a, double b) const { return a + b; } };
-struct FSub { __device__ double operator()(double a, double b) const { return a - b; } };
-struct FMul { __device__ double operator()(double a, double b) const { return a * b; } };
-struct FDiv { __device__ double operator()(double a, double b) const { return a / b; } };
-struct FScale { double s; __device__ double operator()(double a) const { return a * s; } };
-struct FConst { double v; __device__ double operator()(int64_t) const { return v; } };
-// y = alpha*x + beta*y ; beta == 0 never reads y (nalgebra axcpy / the oracle's axpy)
-struct FAxpy { double alpha, beta; __device__ double operator()(double y, double x) const { return alpha * x + beta * y; } };
-struct FAxpy0 { double alpha; __device__ double operator()(double, double x) const { return alpha * x; } };
+// FAdd .. FAxpy0: dsh_ew_ops.hpp (shared with the chain kernel of the op queue)
+using namespace dsh::ew;
 
 template <class F>
 int launch_ternary(dsh_ctx* ctx, int64_t n, int64_t nb, const double* lhs, int64_t lnb, const double* rhs, int64_t rnb, double* ret, F f) {
@@ -353,37 +347,44 @@ __global__ void k_root_finding(int64_t n, int64_t nb, const double* __restrict__
 extern "C" {
 
 int dsh_vec_add(dsh_ctx* ctx, int64_t n, int64_t nb, const double* lhs, int64_t lnb, const double* rhs, int64_t rnb, double* ret) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
   DSH_CHECK_NB(lnb, nb); DSH_CHECK_NB(rnb, nb);
+  if (ctx->opq_on) return opq_enqueue(ctx, opq::OP_ADD, n, nb, ret, nullptr, lhs, lnb, rhs, rnb, 0.0, 0.0);
   return launch_ternary(ctx, n, nb, lhs, lnb, rhs, rnb, ret, FAdd{});
 }
 int dsh_vec_sub(dsh_ctx* ctx, int64_t n, int64_t nb, const double* lhs, int64_t lnb, const double* rhs, int64_t rnb, double* ret) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
   DSH_CHECK_NB(lnb, nb); DSH_CHECK_NB(rnb, nb);
+  if (ctx->opq_on) return opq_enqueue(ctx, opq::OP_SUB, n, nb, ret, nullptr, lhs, lnb, rhs, rnb, 0.0, 0.0);
   return launch_ternary(ctx, n, nb, lhs, lnb, rhs, rnb, ret, FSub{});
 }
 int dsh_vec_add_assign(dsh_ctx* ctx, int64_t n, int64_t nb, double* lhs, const double* rhs, int64_t rnb) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
   DSH_CHECK_NB(rnb, nb);
+  if (ctx->opq_on) return opq_enqueue(ctx, opq::OP_ADD, n, nb, lhs, nullptr, lhs, nb, rhs, rnb, 0.0, 0.0);
   return launch_binary(ctx, n, nb, lhs, rhs, rnb, FAdd{});
 }
 int dsh_vec_sub_assign(dsh_ctx* ctx, int64_t n, int64_t nb, double* lhs, const double* rhs, int64_t rnb) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
   DSH_CHECK_NB(rnb, nb);
+  if (ctx->opq_on) return opq_enqueue(ctx, opq::OP_SUB, n, nb, lhs, nullptr, lhs, nb, rhs, rnb, 0.0, 0.0);
   return launch_binary(ctx, n, nb, lhs, rhs, rnb, FSub{});
 }
 int dsh_vec_mul_assign(dsh_ctx* ctx, int64_t n, int64_t nb, double* lhs, const double* rhs, int64_t rnb) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
   DSH_CHECK_NB(rnb, nb);
+  if (ctx->opq_on) return opq_enqueue(ctx, opq::OP_MUL, n, nb, lhs, nullptr, lhs, nb, rhs, rnb, 0.0, 0.0);
   return launch_binary(ctx, n, nb, lhs, rhs, rnb, FMul{});
 }
 int dsh_vec_div_assign(dsh_ctx* ctx, int64_t n, int64_t nb, double* lhs, const double* rhs, int64_t rnb) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
   DSH_CHECK_NB(rnb, nb);
+  if (ctx->opq_on) return opq_enqueue(ctx, opq::OP_DIV, n, nb, lhs, nullptr, lhs, nb, rhs, rnb, 0.0, 0.0);
   return launch_binary(ctx, n, nb, lhs, rhs, rnb, FDiv{});
 }
 int dsh_vec_mul_assign_scalar(dsh_ctx* ctx, int64_t n, int64_t nb, double* v, double s) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
+  if (ctx->opq_on) return opq_enqueue(ctx, opq::OP_SCALE, n, nb, v, nullptr, v, nb, nullptr, nb, s, 0.0);
   int64_t total = n * nb;
   if (total == 0) return DSH_OK;
   hipLaunchKernelGGL((k_unary<FScale>), ew_grid(total), dim3(kEwBlock), 0, ctx->stream, total, (const double*)v, v, FScale{s});
@@ -391,7 +392,8 @@ int dsh_vec_mul_assign_scalar(dsh_ctx* ctx, int64_t n, int64_t nb, double* v, do
   return DSH_OK;
 }
 int dsh_vec_mul_scalar(dsh_ctx* ctx, int64_t n, int64_t nb, const double* v, double s, double* res) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
+  if (ctx->opq_on) return opq_enqueue(ctx, opq::OP_SCALE, n, nb, res, nullptr, v, nb, nullptr, nb, s, 0.0);
   int64_t total = n * nb;
   if (total == 0) return DSH_OK;
   hipLaunchKernelGGL((k_unary<FScale>), ew_grid(total), dim3(kEwBlock), 0, ctx->stream, total, v, res, FScale{s});
@@ -399,8 +401,9 @@ int dsh_vec_mul_scalar(dsh_ctx* ctx, int64_t n, int64_t nb, const double* v, dou
   return DSH_OK;
 }
 int dsh_vec_axpy(dsh_ctx* ctx, int64_t n, int64_t nb, double alpha, const double* x, int64_t xnb, double beta, double* y) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
   DSH_CHECK_NB(xnb, nb);
+  if (ctx->opq_on) return opq_enqueue(ctx, beta == 0.0 ? opq::OP_AXPY0 : opq::OP_AXPY, n, nb, y, nullptr, x, xnb, y, nb, alpha, beta);
   if (beta == 0.0) return launch_binary(ctx, n, nb, y, x, xnb, FAxpy0{alpha});
   return launch_binary(ctx, n, nb, y, x, xnb, FAxpy{alpha, beta});
 }
@@ -409,14 +412,15 @@ __global__ void k_axpby_to(int64_t total, double alpha, const double* __restrict
                            double* __restrict__ copy_x_to) {
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
     const double xv = x[idx];
-    out[idx] = alpha * xv + beta * y0[idx];
+    out[idx] = dsh::ew::FAxpy{alpha, beta}(y0[idx], xv);
     if (copy_x_to) copy_x_to[idx] = xv;
   }
 }
 int dsh_vec_axpby_to(dsh_ctx* ctx, int64_t n, int64_t nb, double alpha, const double* x, double beta, const double* y0, double* out, double* copy_x_to) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
   DSH_REQUIRE(x && y0 && out, "null argument");
   DSH_REQUIRE(out != x && out != copy_x_to, "dsh_vec_axpby_to: out must not alias x or the copy");
+  if (ctx->opq_on) return opq_enqueue(ctx, opq::OP_AXPY, n, nb, out, copy_x_to, x, nb, y0, nb, alpha, beta);
   const int64_t total = n * nb;
   if (total == 0) return DSH_OK;
   hipLaunchKernelGGL(k_axpby_to, ew_grid(total), dim3(kEwBlock), 0, ctx->stream, total, alpha, x, beta, y0, out, copy_x_to);
@@ -438,13 +442,15 @@ int dsh_vec_batched_axpy(dsh_ctx* ctx, int64_t n, int64_t nb, const double* alph
   return DSH_OK;
 }
 int dsh_vec_copy(dsh_ctx* ctx, int64_t n, int64_t nb, const double* src, int64_t snb, double* dst) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
   DSH_CHECK_NB(snb, nb);
+  if (ctx->opq_on) return opq_enqueue(ctx, snb == nb ? opq::OP_COPY : opq::OP_AXPY0, n, nb, dst, nullptr, src, snb, nullptr, nb, 1.0, 0.0);
   if (snb == nb) return dsh_d2d(ctx, dst, src, sizeof(double) * n * nb);
   return launch_binary(ctx, n, nb, dst, src, snb, FAxpy0{1.0});
 }
 int dsh_vec_fill(dsh_ctx* ctx, int64_t n, int64_t nb, double* v, double value) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
+  if (ctx->opq_on) return opq_enqueue(ctx, opq::OP_FILL, n, nb, v, nullptr, nullptr, nb, nullptr, nb, value, 0.0);
   int64_t total = n * nb;
   if (total == 0) return DSH_OK;
   hipLaunchKernelGGL((k_generate<FConst>), ew_grid(total), dim3(kEwBlock), 0, ctx->stream, total, v, FConst{value});
@@ -452,7 +458,7 @@ int dsh_vec_fill(dsh_ctx* ctx, int64_t n, int64_t nb, double* v, double value) {
   return DSH_OK;
 }
 int dsh_vec_set_index_all(dsh_ctx* ctx, int64_t nb, double* v, int64_t i, double value) {
-  DSH_ENTER(ctx);
+  DSH_ENTER_QUEUE(ctx);
   DSH_REQUIRE(i >= 0, "index out of range");
   return dsh_vec_fill(ctx, 1, nb, v + i * nb, value);
 }

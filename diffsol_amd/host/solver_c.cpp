@@ -91,6 +91,15 @@ int guarded(F&& f) {
     return -1;
   }
 }
+// the same for the entry points that drive a solver: whatever the call left in the op queue of the solver's context (dsh_ctx_set_op_queue) is launched before it returns
+template <class F>
+int guarded_flushed(dshs_solver* s, F&& f) {
+  const int rc = guarded(std::forward<F>(f));
+  if (!s || !s->ctx.raw()) return rc;
+  const int frc = dsh_ctx_flush(s->ctx.raw());
+  if (rc >= 0 && frc != DSH_OK) { g_err = dsh_last_error(); return frc; }
+  return rc;
+}
 // [b][i] host <- device vector
 void download(const HipVec& v, double* host) {
   std::vector<double> tmp = v.clone_as_vec();
@@ -506,6 +515,7 @@ int dshs_create_sens(int device, void* stream, int model, int64_t model_size, in
     s->problem = builder.build_model(model, model_size, p);
     s->method = method;
     s->make_solver();
+    check(dsh_ctx_flush(s->ctx.raw()), "dsh_ctx_flush");
     *out = s.release();
     return 0;
   });
@@ -514,10 +524,12 @@ int dshs_create_sens(int device, void* stream, int model, int64_t model_size, in
 void dshs_destroy(dshs_solver* s) { delete s; }
 
 int dshs_reset(dshs_solver* s) {
-  return guarded([&]() { s->resident_roots_valid = false; s->make_solver(); return 0; });
+  return guarded_flushed(s, [&]() { s->resident_roots_valid = false; s->make_solver(); return 0; });
 }
 dsh_ctx* dshs_context(dshs_solver* s) { return s ? s->ctx.raw() : nullptr; }
 int dshs_set_linear_solve_mode(dshs_solver* s, int mode) { return dsh_ctx_set_solve_mode(s->ctx.raw(), mode); }
+int dshs_set_op_queue(dshs_solver* s, int on) { return dsh_ctx_set_op_queue(s->ctx.raw(), on); }
+int dshs_get_op_queue_stats(dshs_solver* s, int64_t* out) { return dsh_ctx_op_queue_stats(s->ctx.raw(), out); }
 int dshs_set_kernel_timing(dshs_solver* s, int enable) {
   // timed launches bracket the stand-alone Newton kernel: keep the accept launch separate while timing is on
   s->kernel_timing = enable != 0;
@@ -535,7 +547,7 @@ int64_t dshs_nbatch(const dshs_solver* s) { return s->ctx.nbatch(); }
 int dshs_is_fused(const dshs_solver* s) { return s->fused ? 1 : 0; }
 
 int dshs_step(dshs_solver* s, int* stop_reason) {
-  return guarded([&]() {
+  return guarded_flushed(s, [&]() {
     s->resident_roots_valid = false;  // the host solver moves again: dshs_root_info reports ITS events from here on
     OdeSolverStopReason r = s->solver->step();
     if (stop_reason) *stop_reason = (int)r;
@@ -543,13 +555,13 @@ int dshs_step(dshs_solver* s, int* stop_reason) {
   });
 }
 int dshs_set_stop_time(dshs_solver* s, double tstop) {
-  return guarded([&]() { s->resident_roots_valid = false; s->solver->set_stop_time(tstop); return 0; });
+  return guarded_flushed(s, [&]() { s->resident_roots_valid = false; s->solver->set_stop_time(tstop); return 0; });
 }
 int dshs_interpolate(dshs_solver* s, double t, double* y_host) {
-  return guarded([&]() { HipVec y = s->solver->interpolate(t); download(y, y_host); return 0; });
+  return guarded_flushed(s, [&]() { HipVec y = s->solver->interpolate(t); download(y, y_host); return 0; });
 }
 int dshs_get_state(dshs_solver* s, double* t, double* h, int* order, double* y_host, double* dy_host) {
-  return guarded([&]() {
+  return guarded_flushed(s, [&]() {
     if (t) *t = s->solver->t();
     if (h) *h = s->solver->h();
     if (order) *order = s->solver->order();
@@ -560,7 +572,7 @@ int dshs_get_state(dshs_solver* s, double* t, double* h, int* order, double* y_h
 }
 int64_t dshs_nparams(const dshs_solver* s) { return s->problem.eqn->nparams(); }
 int dshs_interpolate_sens(dshs_solver* s, double t, double* s_host) {
-  return guarded([&]() {
+  return guarded_flushed(s, [&]() {
     if ((!s->bdf && !s->sdirk) || !s->problem.sens) throw LaError(DSH_E_INVALID, "the solver was not created with forward sensitivities (dshs_create_sens)");
     const size_t len = (size_t)(s->problem.eqn->nstates() * s->ctx.nbatch());
     const std::vector<HipVec>& cur = s->bdf ? s->bdf->sens() : s->sdirk->sens();
@@ -594,7 +606,7 @@ int dshs_root_info(dshs_solver* s, double* t_root, int* root_index) {
   return 0;
 }
 int dshs_bdf_get_diff(dshs_solver* s, double* diff_host) {
-  return guarded([&]() {
+  return guarded_flushed(s, [&]() {
     if (!s->bdf) throw LaError(DSH_E_INVALID, "not a BDF solver");
     std::vector<double> tmp = s->bdf->diff().clone_as_vec();
     std::memcpy(diff_host, tmp.data(), tmp.size() * sizeof(double));
@@ -614,7 +626,7 @@ int dshs_stats(dshs_solver* s, int64_t* out) {
 }
 
 int dshs_solve_to_points(dshs_solver* s, const double* t_points, int64_t npoints, double* y_host) {
-  return guarded([&]() {
+  return guarded_flushed(s, [&]() {
     s->resident_roots_valid = false;
     const size_t len = (size_t)(s->problem.eqn->nstates() * s->ctx.nbatch());
     for (int64_t k = 0; k < npoints; ++k) {
@@ -633,7 +645,7 @@ int dshs_solve_to_points(dshs_solver* s, const double* t_points, int64_t npoints
 }
 
 int dshs_solve(dshs_solver* s, double final_time, int keep_trajectory, double* y_final_host, int64_t* ncols, int* stop_reason) {
-  return guarded([&]() {
+  return guarded_flushed(s, [&]() {
     s->resident_roots_valid = false;
     OdeSolverStopReason r;
     int64_t cols = 1;
@@ -657,7 +669,7 @@ int dshs_solve(dshs_solver* s, double final_time, int keep_trajectory, double* y
   });
 }
 int dshs_trajectory(dshs_solver* s, double* t_host, double* y_host) {
-  return guarded([&]() {
+  return guarded_flushed(s, [&]() {
     if (s->traj_t.empty()) throw LaError(DSH_E_INVALID, "no trajectory stored (call dshs_solve with keep_trajectory=1)");
     std::memcpy(t_host, s->traj_t.data(), s->traj_t.size() * sizeof(double));
     // device layout [col][row][b] -> host [col][b][row]
@@ -669,7 +681,7 @@ int dshs_trajectory(dshs_solver* s, double* t_host, double* y_host) {
 }
 
 int dshs_solve_dense(dshs_solver* s, const double* t_eval, int64_t nt, double* y_host, double* y_dev, int* stop_reason) {
-  return guarded([&]() {
+  return guarded_flushed(s, [&]() {
     const int mode = resolve_mode(s);
     s->last_mode = mode;
     if (mode != DSHS_ENSEMBLE_LOCKSTEP) {
@@ -743,7 +755,7 @@ int dshs_set_deterministic_pow(int on) {
   return 0;
 }
 int dshs_set_ensemble_mode(dshs_solver* s, int mode) {
-  return guarded([&]() {
+  return guarded_flushed(s, [&]() {
     if (mode != DSHS_ENSEMBLE_AUTO && mode != DSHS_ENSEMBLE_LOCKSTEP && mode != DSHS_ENSEMBLE_PER_MEMBER && mode != DSHS_ENSEMBLE_WAVEFRONT)
       throw LaError(DSH_E_INVALID, "dshs_set_ensemble_mode: mode must be DSHS_ENSEMBLE_AUTO, _LOCKSTEP, _PER_MEMBER or _WAVEFRONT");
     if (mode == DSHS_ENSEMBLE_LOCKSTEP && s->method == DSHS_METHOD_TSIT45) throw LaError(DSH_E_UNSUPPORTED, kTsit45HostDriven);
@@ -768,7 +780,7 @@ int dshs_last_solve_info(const dshs_solver* s, int* mode, int64_t* totals) {
 // parameters, tolerances, options, t0, h0) is the solver's OdeSolverProblem, nothing of the lock-step solver state is touched.
 int dshs_solve_dense_adaptive(dshs_solver* s, const double* t_eval, int64_t nt, int group, int deterministic_pow, double* y_host, double* y_dev, int32_t* stats_host,
                               int32_t* status_host, double* t_root_host, int32_t* root_idx_host, int32_t* ncols_host, int64_t* totals) {
-  return guarded([&]() {
+  return guarded_flushed(s, [&]() {
     int64_t tot[6];
     s->resident_roots_valid = false;  // this call hands the per-member events to the caller's arrays; dshs_root_info falls back to the host solver's
     run_resident(s, t_eval, nt, group, deterministic_pow, y_host, y_dev, stats_host, status_host, t_root_host, root_idx_host, ncols_host, tot);
@@ -782,7 +794,7 @@ int dshs_solve_dense_adaptive(dshs_solver* s, const double* t_eval, int64_t nt, 
 // member order; the problem is the solver's OdeSolverProblem, nothing of the lock-step solver state is touched.
 int dshs_solve_adaptive(dshs_solver* s, double t_final, int64_t max_cols, int group, int deterministic_pow, double* y_host, double* t_host, int32_t* ncols_host,
                         int32_t* stats_host, int32_t* status_host, double* t_root_host, int32_t* root_idx_host, int64_t* totals) {
-  return guarded([&]() {
+  return guarded_flushed(s, [&]() {
     if (!y_host || !t_host || !ncols_host || max_cols < 2) throw LaError(DSH_E_INVALID, "dshs_solve_adaptive: y_host, t_host, ncols_host and max_cols >= 2 are needed");
     if (s->problem.sens) throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_adaptive: without forward sensitivities (dshs_solve walks the host-driven path for the rest)");
     const ResidentPick pk = pick_resident(s, group);
@@ -849,7 +861,7 @@ int dshs_solve_adaptive(dshs_solver* s, double t_final, int64_t max_cols, int gr
 
 int dshs_solve_dense_adaptive_sens(dshs_solver* s, const double* t_eval, int64_t nt, int group, int deterministic_pow, double* y_host, double* sens_host,
                                    int32_t* stats_host, int32_t* status_host, int64_t* totals) {
-  return guarded([&]() {
+  return guarded_flushed(s, [&]() {
     if (!s->problem.sens) throw LaError(DSH_E_INVALID, "the solver was not created with forward sensitivities (dshs_create_sens)");
     if (!sens_host) throw LaError(DSH_E_INVALID, "dshs_solve_dense_adaptive_sens: sens_host is null");
     int64_t tot[6];

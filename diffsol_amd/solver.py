@@ -51,7 +51,7 @@ class Solver:
     """One ensemble solver instance on one GPU."""
 
     def __init__(self, model, p, *, nbatch=1, model_size=0, rtol=1e-6, atol=(1e-6,), t0=0.0, h0=1.0, method=METHOD_BDF, device=0, stream=None,
-                 fused=True, block_threads=0, options=None, ensemble_mode=None, sens=False, sens_rtol=None, sens_atol=None):
+                 fused=True, block_threads=0, options=None, ensemble_mode=None, sens=False, sens_rtol=None, sens_atol=None, op_queue=False):
         L = _ffi.load_host_lib()
         self._L = L
         if isinstance(model, str):
@@ -85,6 +85,22 @@ class Solver:
         self.fused = bool(L.dshs_is_fused(h))
         if ensemble_mode is not None:
             self.set_ensemble_mode(ensemble_mode)
+        if op_queue:
+            self.set_op_queue(True)
+
+    OP_QUEUE_STATS = ("ops_enqueued", "chain_launches", "hazard_flushes", "entry_flushes")
+
+    def set_op_queue(self, on):
+        """dshs_set_op_queue: deferred execution of the element-wise vector operations of the host-driven (lock-step, trait-operation) integrators — recorded and
+        launched as chains, one kernel per run, instead of one kernel each; bit-identical results.  Off by default; switching resets op_queue_stats()."""
+        check(self._L.dshs_set_op_queue(self._h, 1 if on else 0), host=True)
+
+    def op_queue_stats(self):
+        """counters of the op queue since it was last switched: operations recorded, chain launches, launches forced by an operation that could not join the chain
+        (hazard, other shape, full chain), launches forced by a call that does not queue"""
+        out = (C.c_int64 * 4)()
+        check(self._L.dshs_get_op_queue_stats(self._h, out), host=True)
+        return dict(zip(self.OP_QUEUE_STATS, [int(v) for v in out]))
 
     def set_ensemble_mode(self, mode):
         """ENSEMBLE_AUTO (default): solve_dense runs device-resident whenever the model has such a kernel; ENSEMBLE_LOCKSTEP: host-driven trait path."""

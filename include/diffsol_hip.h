@@ -95,6 +95,21 @@ int dsh_ctx_get_timing(dsh_ctx* ctx, int64_t* launches, double* total_ms);
  * measurement that is not the kernel; and the summed duration of the same timed launches measured inside the kernel with the 100 MHz
  * device clock (max workgroup end - min workgroup start), which is what rocprofv3's kernel trace reports */
 int dsh_ctx_get_timing_overhead(dsh_ctx* ctx, double* empty_bracket_ms, double* device_clock_total_ms);
+/* Deferred execution of the element-wise operations (op queue; OFF by default, environment DSH_OP_QUEUE=1 switches the initial mode of every context on).
+ * While the mode is on, dsh_vec_add / _sub / _add_assign / _sub_assign / _mul_assign / _div_assign / _mul_scalar / _mul_assign_scalar / _axpy / _axpby_to /
+ * _copy / _fill / _set_index_all, dsh_mat_set_column / _column_axpy / _scale_add_assign and dsh_d2d (pointers and size multiples of 8) validate their
+ * arguments as always and then only RECORD the operation; the recorded run is executed as one kernel launch by the next call that is not one of them (every
+ * other entry point of this header launches the queue first, so the host and every other kernel see finished work), by an operation that could not share a
+ * launch with the recorded ones (another shape, a partially overlapping operand, a full queue of 32), or by dsh_ctx_flush.  Results are bit-identical to the
+ * immediate mode.  A failure of the queued launch is reported by the call that caused it (dsh_last_error names k_op_chain).  dsh_ctx_stream launches the queue
+ * too; a caller that keeps the stream handle and issues work of its own on it later calls dsh_ctx_flush first.
+ * dsh_ctx_set_op_queue: switching (either way) launches what is queued and resets the counters.  dsh_ctx_get_op_queue: 1 / 0 (-1: null context).
+ * dsh_ctx_op_queue_stats: out[0] operations recorded, out[1] queue launches, out[2] launches forced by an operation that could not join (hazard, other
+ * shape, queue full), out[3] launches forced by a call that does not queue. */
+int dsh_ctx_set_op_queue(dsh_ctx* ctx, int on);
+int dsh_ctx_get_op_queue(const dsh_ctx* ctx);
+int dsh_ctx_flush(dsh_ctx* ctx);
+int dsh_ctx_op_queue_stats(dsh_ctx* ctx, int64_t* out /* 4 values */);
 
 /* ---- device memory (cudarc alloc/alloc_zeros/memcpy_*: call sites throughout vector/cuda.rs, matrix/cuda.rs) ---- */
 int dsh_malloc(dsh_ctx* ctx, int64_t nbytes, int zero, void** out);

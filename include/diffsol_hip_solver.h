@@ -80,6 +80,11 @@ int dshs_reset(dshs_solver* s);
 dsh_ctx* dshs_context(dshs_solver* s);
 /* dsh_ctx_set_solve_mode of the solver's context: DSH_SOLVE_EXACT (default, bit-identical to the CPU path) | DSH_SOLVE_REORDERED (opt-in, tolerance-level differences) */
 int dshs_set_linear_solve_mode(dshs_solver* s, int mode);
+/* dsh_ctx_set_op_queue / dsh_ctx_op_queue_stats of the solver's context: the host-driven (lock-step, trait-operation) integrators then issue their element-wise
+ * vector operations as chains, bit-identical results.  Every dshs_* call returns with the queue empty: a caller that reads an output pointer on the solver's stream
+ * afterwards sees finished work. */
+int dshs_set_op_queue(dshs_solver* s, int on);
+int dshs_get_op_queue_stats(dshs_solver* s, int64_t* out /* 4 values */);
 int dshs_set_kernel_timing(dshs_solver* s, int enable);
 int dshs_set_kernel_timing_target(dshs_solver* s, int target); /* DSH_TIMING_* of diffsol_hip.h */
 int dshs_get_kernel_timing(dshs_solver* s, int64_t* launches, double* total_ms);

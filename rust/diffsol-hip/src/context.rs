@@ -61,6 +61,15 @@ impl HipContext {
     pub fn synchronize(&self) {
         check(unsafe { ffi::dsh_ctx_sync(self.ptr()) }, "dsh_ctx_sync");
     }
+    /// Deferred execution of the element-wise trait operations (`dsh_ctx_set_op_queue`, off by default): `Vector` / `Matrix` operations are recorded and
+    /// launched as chains, one kernel per run, by the next operation whose result the host or another kernel needs.  Results are bit-identical.
+    pub fn set_op_queue(&self, on: bool) {
+        check(unsafe { ffi::dsh_ctx_set_op_queue(self.ptr(), on as i32) }, "dsh_ctx_set_op_queue");
+    }
+    /// Launch what the op queue holds (`dsh_ctx_flush`): needed only before issuing work of one's own on the context's stream.
+    pub fn flush(&self) {
+        check(unsafe { ffi::dsh_ctx_flush(self.ptr()) }, "dsh_ctx_flush");
+    }
     /// Two contexts are the same device context if they share the handle (the `nbatch` may differ: broadcast operands).
     pub(crate) fn same_device_context(&self, other: &Self) -> bool {
         Arc::ptr_eq(&self.raw, &other.raw)

@@ -47,6 +47,11 @@ struct JitModelRec {
   int64_t member_twin_dims[4] = {0, 0, 0, 0};  // n, nparams, nroots, nout
   int member_twin = -1;
   bool member_twin_failed = false;
+  // output sensitivities (dsh_model_set_out_sens_source): a source of its own — jit_out_component, jit_out_jac_component, jit_out_sens_component — compiled behind
+  // dsh_out_sens_kernel.hpp at the first dsh_model_out_sens.  Separate from `source`: registering it changes no translation unit of the integrator modules
+  std::string out_sens_source;
+  std::unique_ptr<JitModule> out_sens_module;
+  bool out_sens_failed = false;
 };
 
 std::mutex g_mu;
@@ -343,6 +348,20 @@ JitModelRec* find_model(int model) {
   return it == g_models.end() ? nullptr : it->second.get();
 }
 
+// the output-sensitivity module of a model (registry lock held): <registered source> + dsh_out_sens_kernel.hpp, compiled once
+int ensure_out_sens_module(JitModelRec* rec) {
+  if (rec->out_sens_module) return DSH_OK;
+  if (rec->out_sens_source.empty()) { set_error("the model has no output-sensitivity source (dsh_model_set_out_sens_source)"); return DSH_E_UNSUPPORTED; }
+  auto m = std::make_unique<JitModule>();
+  const std::string tu = "#include <hip/hip_runtime.h>\n#include \"diffsol_detpow.h\"\n" + rec->out_sens_source + "\n#include \"dsh_out_sens_kernel.hpp\"\n";
+  const std::vector<std::string> none;
+  record_request(tu, "dsh_out_sens_kernel.hpp", none);
+  const int rc = compile_tu(*rec, tu, "dsh_out_sens_kernel.hpp", none, m.get());
+  if (rc != DSH_OK) { rec->out_sens_failed = true; return rc; }
+  rec->out_sens_module = std::move(m);
+  return DSH_OK;
+}
+
 const char* ops_header(int form) { return form == DSH_JIT_FORM_STATIC ? "dsh_model_kernels.hpp" : "dsh_jit_dyn_kernels.hpp"; }
 
 }  // namespace
@@ -554,6 +573,94 @@ int dsh_model_member_twin(int model_id) {
   return ret;
 }
 
+// ---- output sensitivities: out_i and d(out_i)/dp at every save point from one launch (dsh_out_sens_kernel.hpp; sensitivities.rs:360-397 of the reference)
+int dsh_model_set_out_sens_source(int model_id, const char* source) {
+  DSH_REQUIRE(source != nullptr && *source, "the source is empty");
+  std::lock_guard<std::mutex> lk(g_mu);
+  JitModelRec* rec = find_model(model_id);
+  if (!rec) { set_error("dsh_model_set_out_sens_source: unknown model id"); return DSH_E_INVALID; }
+  DSH_REQUIRE(rec->info.nout >= 1, "the model has no out_i");
+  if (rec->out_sens_module && rec->out_sens_module->module) (void)hipModuleUnload(rec->out_sens_module->module);
+  rec->out_sens_module.reset();
+  rec->out_sens_failed = false;
+  // the stated dimensions must be the ones the source was generated with
+  rec->out_sens_source = std::string(source) + "\nstatic_assert(dsh::kOutSensN == " + std::to_string(rec->info.n) + " && dsh::kOutSensNP == " + std::to_string(rec->info.np) +
+                         " && dsh::kOutSensNOut == " + std::to_string(rec->info.nout) + ", \"dsh_model_set_out_sens_source: dimensions do not match the model\");\n";
+  return DSH_OK;
+}
+int dsh_model_has_out_sens(int model_id) {
+  if (!is_jit_model(model_id)) return 0;
+  std::lock_guard<std::mutex> lk(g_mu);
+  JitModelRec* rec = find_model(model_id);
+  return rec && !rec->out_sens_source.empty() ? 1 : 0;
+}
+int dsh_model_out_sens_dims(int model_id, int64_t* nstates, int64_t* nparams, int64_t* nout) {
+  if (!dsh_model_has_out_sens(model_id)) { set_error("dsh_model_out_sens_dims: the model has no output-sensitivity source (dsh_model_set_out_sens_source)"); return DSH_E_UNSUPPORTED; }
+  std::lock_guard<std::mutex> lk(g_mu);
+  JitModelRec* rec = find_model(model_id);
+  if (!rec) { set_error("dsh_model_out_sens_dims: unknown model id"); return DSH_E_INVALID; }
+  if (nstates) *nstates = rec->info.n;
+  if (nparams) *nparams = rec->info.np;
+  if (nout) *nout = rec->info.nout;
+  return DSH_OK;
+}
+int dsh_model_out_sens_strided(dsh_ctx* ctx, int model, int64_t nb, int64_t ncols, const double* t_cols_host, const double* y, const double* sens, int64_t sens_param_stride,
+                               int64_t sens_col_stride, const double* p, const int32_t* member_cols, double* out, double* dout) {
+  DSH_ENTER(ctx);
+  DSH_REQUIRE(ctx != nullptr, "ctx is null");
+  DSH_REQUIRE(nb >= 0 && ncols >= 0, "negative extent");
+  if (!dsh_model_has_out_sens(model)) {
+    set_error("dsh_model_out_sens: the model has no output-sensitivity source (a DiffSL model with inputs and an out_i registers one: dsh_model_set_out_sens_source)");
+    return DSH_E_UNSUPPORTED;
+  }
+  if (nb == 0 || ncols == 0) return DSH_OK;
+  DSH_REQUIRE(t_cols_host && y && sens && p && out && dout, "null argument");
+  hipFunction_t f = nullptr;
+  int64_t n = 0;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    JitModelRec* rec = find_model(model);
+    if (!rec) { set_error("dsh_model_out_sens: unknown model id"); return DSH_E_INVALID; }
+    if (rec->out_sens_failed) { set_error("dsh_model_out_sens: the output-sensitivity source of this model did not compile"); return DSH_E_INVALID; }
+    n = rec->info.n;
+    const int crc = ensure_out_sens_module(rec);  // first request: compile (or load from the on-disk cache)
+    if (crc != DSH_OK) return crc;
+    JitModule& m = *rec->out_sens_module;
+    if (!m.module) DSH_HIP_CHECK(hipModuleLoadData(&m.module, m.code.data()));
+    auto it = m.functions.find("k_out_sens");
+    if (it == m.functions.end()) {
+      hipFunction_t fn = nullptr;
+      DSH_HIP_CHECK(hipModuleGetFunction(&fn, m.module, "k_out_sens"));
+      it = m.functions.emplace("k_out_sens", fn).first;
+    }
+    f = it->second;
+  }
+  DSH_REQUIRE(sens_param_stride >= 0 && sens_col_stride >= n * nb, "the sensitivity strides must leave room for one n x nbatch block per column");
+  double* t_dev = nullptr;
+  int rc = dsh_malloc(ctx, (int64_t)sizeof(double) * ncols, 0, (void**)&t_dev);
+  if (rc != DSH_OK) return rc;
+  struct Release { dsh_ctx* c; void* q; ~Release() { dsh_free(c, q); } } release{ctx, t_dev};
+  DSH_HIP_CHECK(hipMemcpyAsync(t_dev, t_cols_host, sizeof(double) * (size_t)ncols, hipMemcpyHostToDevice, ctx->stream));
+  const unsigned block = 256;
+  const dim3 grid((unsigned)((nb + block - 1) / block), (unsigned)std::min<int64_t>(ncols, 65535));
+  long long nb_ = nb, ncols_ = ncols, sj = sens_param_stride, sc = sens_col_stride;
+  const double* t_c = t_dev;
+  void* argv[] = {&nb_, &ncols_, &t_c, &y, &sens, &sj, &sc, &p, &member_cols, &out, &dout};
+  rc = timed_call(ctx, 0, [&]() -> int {
+    DSH_HIP_CHECK(hipModuleLaunchKernel(f, grid.x, grid.y, 1, block, 1, 1, 0, ctx->stream, argv, nullptr));
+    return DSH_OK;
+  });
+  if (rc != DSH_OK) return rc;
+  DSH_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // t_cols_host is the caller's: it may go away when this returns
+  return DSH_OK;
+}
+int dsh_model_out_sens(dsh_ctx* ctx, int model, int64_t nb, int64_t ncols, const double* t_cols_host, const double* y, const double* sens, const double* p,
+                       const int32_t* member_cols, double* out, double* dout) {
+  int64_t n = 0;
+  if (dsh_model_has_out_sens(model) && dsh_model_out_sens_dims(model, &n, nullptr, nullptr) != DSH_OK) return DSH_E_INVALID;
+  return dsh_model_out_sens_strided(ctx, model, nb, ncols, t_cols_host, y, sens, ncols * n * nb, n * nb, p, member_cols, out, dout);
+}
+
 int dsh_model_release(int model_id) {
   {
     int tw = -1;
@@ -569,11 +676,12 @@ int dsh_model_release(int model_id) {
   if (it == g_models.end()) { set_error("dsh_model_release: unknown model id"); return DSH_E_INVALID; }
   for (auto& kv : it->second->modules)
     if (kv.second && kv.second->module) (void)hipModuleUnload(kv.second->module);
+  if (it->second->out_sens_module && it->second->out_sens_module->module) (void)hipModuleUnload(it->second->out_sens_module->module);
   g_models.erase(it);
   return DSH_OK;
 }
 
-// compile (not load) one kernel family of a run-time-compiled model: 0 operators, 1 fused Newton kernels, 2 resident BDF, 3 resident SDIRK.
+// compile (not load) one kernel family of a run-time-compiled model: 0 operators, 1 fused Newton kernels, 2 resident BDF, 3 resident SDIRK, 4 output sensitivities.
 // Needs no GPU; used by the build check and by callers that want to pay the compilation before the first solve.
 int64_t dsh_jit_compile_count(void) { return (int64_t)g_jit_compiles.load(); }
 
@@ -626,6 +734,7 @@ int dsh_model_precompile(int model_id, int family) {
   std::lock_guard<std::mutex> lk(g_mu);
   JitModelRec* rec = find_model(model_id);
   if (!rec) { set_error("dsh_model_precompile: unknown model id"); return DSH_E_INVALID; }
+  if (family == 4) return ensure_out_sens_module(rec);  // output sensitivities (dsh_model_out_sens), any form
   struct Unit { const char* header; std::string key; std::vector<std::string> group; };
   std::vector<Unit> units;
   const bool st = rec->info.form == DSH_JIT_FORM_STATIC;

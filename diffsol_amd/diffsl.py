@@ -14,8 +14,10 @@ from . import _ffi
 from ._ffi import check, vp
 
 TARGET_HIP_STATIC, TARGET_HIP_DYNAMIC, TARGET_HOST_C = 0, 1, 2
+# output sensitivities (models with inputs and an out_i): the device source of csrc/dsh_out_sens_kernel.hpp and its extern "C" CPU twin
+TARGET_HIP_OUT_SENS, TARGET_HOST_OUT_SENS = 3, 4
 FORM_STATIC, FORM_DYNAMIC, FORM_STATIC_BANDED = 0, 1, 2
-FAMILY_OPERATORS, FAMILY_FUSED, FAMILY_RESIDENT_BDF, FAMILY_RESIDENT_SDIRK = 0, 1, 2, 3
+FAMILY_OPERATORS, FAMILY_FUSED, FAMILY_RESIDENT_BDF, FAMILY_RESIDENT_SDIRK, FAMILY_OUT_SENS = 0, 1, 2, 3, 4
 
 
 def generate(code, target, model_index=0):
@@ -72,6 +74,10 @@ class DiffslModel:
             # compiled by the library at the first such request
             dyn_src = generate(code, TARGET_HIP_DYNAMIC, model_index)[0]
             check(self._L.dsh_model_set_member_twin_source(self.model_id, dyn_src.encode(), self.n, self.nparams, self.nroots, self.nout))
+        self.has_out_sens = self.nout > 0 and not self.no_inputs
+        if self.has_out_sens:
+            # out_i and d(out_i)/dp on the device (Solver.solve_dense_sens_outputs): the source is only registered here, the library compiles it at the first request
+            check(self._L.dsh_model_set_out_sens_source(self.model_id, generate(code, TARGET_HIP_OUT_SENS, model_index)[0].encode()))
 
     def precompile(self, family):
         """Compile a kernel family now instead of at its first launch (needs no GPU)."""
@@ -88,3 +94,7 @@ class DiffslModel:
     def host_source(self):
         """The same model as an `extern "C"` CPU library source (dsl_rhs, dsl_jac_mul, ...): what the parity tests hand to the CPU oracle."""
         return generate(self.code, TARGET_HOST_C)[0]
+
+    def out_sens_host_source(self):
+        """The output sensitivities as an `extern "C"` CPU library source (dsl_out, dsl_out_jac_mul, dsl_out_sens_mul): the checker of the device kernel."""
+        return generate(self.code, TARGET_HOST_OUT_SENS, self.model_index)[0]

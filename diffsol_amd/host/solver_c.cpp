@@ -310,12 +310,25 @@ dsh_adaptive_options adaptive_options_of(const dshs_solver* s, int group, int de
   return o;
 }
 
+// dshs_solve_dense_sens_out: the outputs and their sensitivities computed on the device from the states and sensitivities of the launch (dsh_model_out_sens)
+struct OutSensSpec {
+  int model = 0;       // the model that carries the output-sensitivity source
+  int64_t nout = 0;
+  double* out_host = nullptr;   // [nt][b][nout]
+  double* dout_host = nullptr;  // [nparams][nt][b][nout]
+};
+// device [col][k][b] blocks -> host [col][b][k], block by block (the blocks of dout, [j][col], are in the same order on both sides)
+void download_blocks(dsh_ctx* c, int64_t nblocks, int64_t rows, int64_t nb, const double* dev, double* host) {
+  for (int64_t k = 0; k < nblocks; ++k) check(dsh_vec_download(c, rows, nb, dev + (size_t)(k * rows * nb), host + (size_t)(k * rows * nb)), "output sensitivities download");
+}
+
 // lazy: status_host is fetched only when a member failed (totals[5] != 0; it is all zero otherwise) and root_idx_host only for models with root
 // functions (all -1 otherwise): the common case of dshs_solve_dense then moves no per-member bookkeeping over PCIe at all.
 void run_resident(dshs_solver* s, const double* t_eval, int64_t nt, int group, int deterministic_pow, double* y_host, double* y_dev, int32_t* stats_host,
-                  int32_t* status_host, double* t_root_host, int32_t* root_idx_host, int32_t* ncols_host, int64_t* totals, bool lazy = false, double* sens_host = nullptr) {
+                  int32_t* status_host, double* t_root_host, int32_t* root_idx_host, int32_t* ncols_host, int64_t* totals, bool lazy = false, double* sens_host = nullptr,
+                  const OutSensSpec* out_sens = nullptr) {
   const ResidentPick pk = pick_resident(s, group);
-  if (s->problem.sens && (!pk.ok || !sens_host))
+  if (s->problem.sens && (!pk.ok || (!sens_host && !out_sens)))
     throw LaError(DSH_E_UNSUPPORTED, "device-resident integration with forward sensitivities: dshs_solve_dense_adaptive_sens, BDF, static ODE models with parameter "
                                      "derivatives (n <= 4, no root functions); other problems integrate their sensitivities host-driven (dshs_solve_dense + dshs_interpolate_sens)");
   if (!pk.ok)
@@ -335,11 +348,11 @@ void run_resident(dshs_solver* s, const double* t_eval, int64_t nt, int group, i
   // every device buffer of this call is released when the function leaves, also by the exceptions check() throws between the allocations (an out-of-memory on
   // the second output buffer is exactly when leaking the first one would hurt)
   void *tmp_out = nullptr, *sorted_out = nullptr, *stats_dev = nullptr, *status_dev = nullptr, *troot_dev = nullptr, *ridx_dev = nullptr, *ncols_dev = nullptr, *sens_dev = nullptr,
-       *sens_sorted = nullptr;
+       *sens_sorted = nullptr, *outs_dev = nullptr, *douts_dev = nullptr;
   struct Release {
     dsh_ctx* c; std::vector<void**> bufs;
     ~Release() { for (void** q : bufs) if (*q) dsh_free(c, *q); }
-  } release{c, {&tmp_out, &sorted_out, &stats_dev, &status_dev, &troot_dev, &ridx_dev, &ncols_dev, &sens_dev, &sens_sorted}};
+  } release{c, {&tmp_out, &sorted_out, &stats_dev, &status_dev, &troot_dev, &ridx_dev, &ncols_dev, &sens_dev, &sens_sorted, &outs_dev, &douts_dev}};
   if (!out) { check(dsh_malloc(c, (int64_t)sizeof(double) * nt * n * nb, 0, &tmp_out), "adaptive out"); out = (double*)tmp_out; }
   double* user_out = out;
   if (sorted) { check(dsh_malloc(c, (int64_t)sizeof(double) * nt * n * nb, 0, &sorted_out), "adaptive out (sorted)"); out = (double*)sorted_out; }
@@ -372,7 +385,7 @@ void run_resident(dshs_solver* s, const double* t_eval, int64_t nt, int group, i
                                          (int32_t*)status_dev, totals);
     if (rc == DSH_OK && sorted) rc = dsh_permute_members(c, nt * npar * n, nb, 8, sens_sorted, (const int32_t*)s->inv_dev, sens_dev);
     // [col][parameter][state][b] on the device -> [parameter][col][b][state] on the host (one y-shaped array per parameter: solve_dense_sensitivities' Vec<M>)
-    for (int64_t k = 0; k < nt && rc == DSH_OK; ++k)
+    for (int64_t k = 0; k < nt && rc == DSH_OK && sens_host; ++k)
       for (int64_t q = 0; q < npar && rc == DSH_OK; ++q)
         rc = dsh_vec_download(c, n, nb, (const double*)sens_dev + (size_t)((k * npar + q) * n * nb), sens_host + (size_t)((q * nt + k) * n * nb));
   } else
@@ -405,6 +418,18 @@ void run_resident(dshs_solver* s, const double* t_eval, int64_t nt, int group, i
     out = user_out;
     back(stats_dev, 5, 4); back(status_dev, 1, 4); back(troot_dev, 1, 8); back(ridx_dev, 1, 4); back(ncols_dev, 1, 4);
   }
+  if (rc == DSH_OK && out_sens) {
+    // states (`out`, [col][state][b]) and sensitivities (sens_dev, [col][parameter][state][b]) are in the caller's member order by now and never left the device:
+    // one launch maps them to the outputs and their sensitivities, and only those travel (a failed member's columns hold NaN and stay NaN through the arithmetic)
+    check(dsh_malloc(c, (int64_t)sizeof(double) * nt * out_sens->nout * nb, 0, &outs_dev), "output sensitivities (out)");
+    check(dsh_malloc(c, (int64_t)sizeof(double) * npar * nt * out_sens->nout * nb, 0, &douts_dev), "output sensitivities (dout)");
+    rc = dsh_model_out_sens_strided(c, out_sens->model, nb, nt, t_eval, out, (const double*)sens_dev, n * nb, npar * n * nb, s->problem.eqn->params().ptr(), nullptr,
+                                    (double*)outs_dev, (double*)douts_dev);
+    if (rc == DSH_OK) {
+      download_blocks(c, nt, out_sens->nout, nb, (const double*)outs_dev, out_sens->out_host);
+      download_blocks(c, npar * nt, out_sens->nout, nb, (const double*)douts_dev, out_sens->dout_host);
+    }
+  }
   if (rc == DSH_OK && y_host)
     for (int64_t k = 0; k < nt && rc == DSH_OK; ++k) rc = dsh_vec_download(c, n, nb, out + (size_t)(k * n * nb), y_host + (size_t)(k * n * nb));
   if (rc == DSH_OK && stats_host) rc = dsh_d2h(c, stats_host, stats_dev, (int64_t)sizeof(int32_t) * 5 * nb);
@@ -424,10 +449,11 @@ const char* dshs_last_error(void) { return g_err.c_str(); }
 static int diffsl_generate_impl(const char* code, int target, int model_index, char** source_out, int64_t* dims, double* defaults_out, int64_t defaults_cap) {
   return guarded([&] {
     if (!code || !source_out) throw LaError(DSH_E_INVALID, "dshs_diffsl_generate: null argument");
-    if (target < 0 || target > 2) throw LaError(DSH_E_INVALID, "dshs_diffsl_generate: unknown target");
+    if (target < 0 || target > DSHS_DIFFSL_HOST_OUT_SENS) throw LaError(DSH_E_INVALID, "dshs_diffsl_generate: unknown target");
     if (model_index < 0) throw LaError(DSH_E_INVALID, "dshs_diffsl_generate: the model index is unsigned");
     diffsl::Compiled c = diffsl::compile(code, model_index);
-    const diffsl::Target t = target == DSHS_DIFFSL_HIP_STATIC ? diffsl::Target::HipStatic : target == DSHS_DIFFSL_HIP_DYNAMIC ? diffsl::Target::HipDynamic : diffsl::Target::HostC;
+    const diffsl::Target t = target == DSHS_DIFFSL_HIP_STATIC ? diffsl::Target::HipStatic : target == DSHS_DIFFSL_HIP_DYNAMIC ? diffsl::Target::HipDynamic :
+                             target == DSHS_DIFFSL_HIP_OUT_SENS ? diffsl::Target::HipOutSens : target == DSHS_DIFFSL_HOST_OUT_SENS ? diffsl::Target::HostOutSens : diffsl::Target::HostC;
     std::string src = diffsl::generate(c, t);
     char* out = (char*)std::malloc(src.size() + 1);
     if (!out) throw LaError(DSH_E_INVALID, "out of memory");
@@ -869,6 +895,90 @@ int dshs_solve_dense_adaptive_sens(dshs_solver* s, const double* t_eval, int64_t
     run_resident(s, t_eval, nt, group, deterministic_pow, y_host, nullptr, stats_host, status_host, nullptr, nullptr, nullptr, tot, false, sens_host);
     for (int k = 0; k < 6; ++k) { s->last_totals[k] = tot[k]; if (totals) totals[k] = tot[k]; }
     s->last_mode = group;
+    return 0;
+  });
+}
+
+// Output sensitivities (the reference's solve_dense_sensitivities for a model with an out_i, ode_solver/sensitivities.rs:360-397): the device-resident launch with forward
+// sensitivities where the model has one — its states and sensitivities stay on the device — else the host-driven solver stepped and interpolated at the save points;
+// either way ONE launch of k_out_sens (dsh_model_out_sens) maps every column, member and parameter, and only out / dout (and what the caller asks for besides) are copied.
+int dshs_solve_dense_sens_out(dshs_solver* s, const double* t_eval, int64_t nt, int group, int deterministic_pow, double* y_host, double* sens_host, double* out_host,
+                              double* dout_host, int32_t* stats_host, int32_t* status_host, int64_t* totals) {
+  return guarded_flushed(s, [&]() {
+    if (!t_eval || nt < 1 || !out_host || !dout_host) throw LaError(DSH_E_INVALID, "dshs_solve_dense_sens_out: t_eval, out_host and dout_host are needed");
+    if (s->method == DSHS_METHOD_TSIT45) throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_dense_sens_out: Tsit45 has no forward sensitivities; use BDF, TR-BDF2 or ESDIRK34");
+    if (!s->problem.sens) throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_dense_sens_out: the solver was not created with forward sensitivities (dshs_create_sens)");
+    OutSensSpec os;
+    int64_t msize = 0, mn = 0, mnp = 0;
+    if (!s->problem.eqn->registry_model(&os.model, &msize) || !dsh_model_has_out_sens(os.model))
+      throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_dense_sens_out: the model has no output-sensitivity source — it needs a DiffSL model with inputs and an out_i "
+                                       "(dsh_model_set_out_sens_source); built-in registry models have no out_i");
+    check(dsh_model_out_sens_dims(os.model, &mn, &mnp, &os.nout), "dsh_model_out_sens_dims");
+    if (s->problem.eqn->has_reset()) throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_dense_sens_out: the model has a reset_i; sensitivities across resets are not supported");
+    os.out_host = out_host; os.dout_host = dout_host;
+    const int64_t n = s->problem.eqn->nstates(), nb = s->ctx.nbatch(), npar = s->problem.eqn->nparams();
+    if (mn != n || mnp != npar) throw LaError(DSH_E_INVALID, "dshs_solve_dense_sens_out: the output-sensitivity source does not belong to this model");
+    for (int64_t k = 0; k + 1 < nt; ++k) if (t_eval[k] > t_eval[k + 1]) throw LaError(DSH_E_INVALID, "dshs_solve_dense_sens_out: t_eval must be increasing");
+    if (t_eval[0] < s->problem.t0) throw LaError(DSH_E_INVALID, "dshs_solve_dense_sens_out: t_eval must not start before t0");
+    int64_t tot[6] = {0, 0, 0, 0, 0, 0};
+    s->resident_roots_valid = false;
+    if (pick_resident(s, group).ok) {
+      run_resident(s, t_eval, nt, group, deterministic_pow, y_host, nullptr, stats_host, status_host, nullptr, nullptr, nullptr, tot, false, sens_host, &os);
+      s->last_mode = group;
+    } else {
+      // host-driven: a fresh solver from (t0, y0), stepped to the last save point; states and sensitivities interpolated at every save point the step has passed
+      // (the loop of diffsol_ode_solve_fwd_sens, on device columns)
+      if (s->solver->get_statistics().number_of_steps != 0 || s->solver->t() != s->problem.t0) s->make_solver();
+      dsh_ctx* c = s->ctx.raw();
+      void *y_dev = nullptr, *sens_dev = nullptr, *outs_dev = nullptr, *douts_dev = nullptr;
+      struct Release {
+        dsh_ctx* c; std::vector<void**> bufs;
+        ~Release() { for (void** q : bufs) if (*q) dsh_free(c, *q); }
+      } release{c, {&y_dev, &sens_dev, &outs_dev, &douts_dev}};
+      const int64_t col_bytes = (int64_t)sizeof(double) * n * nb;
+      check(dsh_malloc(c, col_bytes * nt, 0, &y_dev), "sens_out states");
+      check(dsh_malloc(c, col_bytes * nt * npar, 0, &sens_dev), "sens_out sensitivities");  // [parameter][col][state][b]
+      check(dsh_malloc(c, (int64_t)sizeof(double) * nt * os.nout * nb, 0, &outs_dev), "sens_out out");
+      check(dsh_malloc(c, (int64_t)sizeof(double) * npar * nt * os.nout * nb, 0, &douts_dev), "sens_out dout");
+      int64_t col = 0;
+      std::vector<HipVec> sv;
+      auto drain = [&](double upto) {
+        while (col < nt && t_eval[col] <= upto) {
+          HipVec y = s->solver->interpolate(t_eval[col]);
+          check(dsh_d2d(c, (double*)y_dev + (size_t)(col * n * nb), y.ptr(), col_bytes), "sens_out d2d");
+          sv.clear();
+          if (s->bdf) s->bdf->interpolate_sens_inplace(t_eval[col], sv); else s->sdirk->interpolate_sens_inplace(t_eval[col], sv);
+          if ((int64_t)sv.size() != npar) throw LaError(DSH_E_INVALID, "dshs_solve_dense_sens_out: the solver carries no sensitivities");
+          for (int64_t j = 0; j < npar; ++j) check(dsh_d2d(c, (double*)sens_dev + (size_t)((j * nt + col) * n * nb), sv[(size_t)j].ptr(), col_bytes), "sens_out d2d");
+          ++col;
+        }
+      };
+      drain(s->solver->t());
+      if (col < nt) {
+        s->solver->set_stop_time(t_eval[nt - 1]);
+        while (true) {
+          const OdeSolverStopReason r = s->solver->step();
+          if (r == OdeSolverStopReason::RootFound)
+            throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_dense_sens_out: a stop condition fired before the last save point; events with forward sensitivities are not supported");
+          drain(s->solver->t());
+          if (r == OdeSolverStopReason::TstopReached) break;
+        }
+      }
+      check(dsh_model_out_sens(c, os.model, nb, nt, t_eval, (const double*)y_dev, (const double*)sens_dev, s->problem.eqn->params().ptr(), nullptr, (double*)outs_dev,
+                               (double*)douts_dev), "dsh_model_out_sens");
+      download_blocks(c, nt, os.nout, nb, (const double*)outs_dev, out_host);
+      download_blocks(c, npar * nt, os.nout, nb, (const double*)douts_dev, dout_host);
+      if (y_host) download_blocks(c, nt, n, nb, (const double*)y_dev, y_host);
+      if (sens_host) download_blocks(c, npar * nt, n, nb, (const double*)sens_dev, sens_host);
+      const OdeSolverStatistics& st = s->solver->get_statistics();
+      const int64_t per[5] = {(int64_t)st.number_of_steps, (int64_t)st.number_of_nonlinear_solver_iterations, (int64_t)st.number_of_linear_solver_setups,
+                              (int64_t)st.number_of_error_test_failures, (int64_t)st.number_of_nonlinear_solver_fails};
+      for (int k = 0; k < 5; ++k) tot[k] = per[k] * nb;
+      if (stats_host) for (int k = 0; k < 5; ++k) for (int64_t b = 0; b < nb; ++b) stats_host[(size_t)(k * nb + b)] = (int32_t)per[k];
+      if (status_host) std::fill(status_host, status_host + nb, 0);
+      s->last_mode = DSHS_ENSEMBLE_LOCKSTEP;
+    }
+    for (int k = 0; k < 6; ++k) { s->last_totals[k] = tot[k]; if (totals) totals[k] = tot[k]; }
     return 0;
   });
 }

@@ -282,6 +282,32 @@ class Solver:
         tot = dict(zip(self.ADAPTIVE_TOTALS, [int(v) for v in totals]))
         return (out, sens, tot, m) if want_member_stats else (out, sens, tot)
 
+    def solve_dense_sens_outputs(self, t_eval, group=1, deterministic_pow=True, want_states=False, want_member_stats=False):
+        """solve_dense_sensitivities for a model with an out_i (sensitivities.rs:360-397; dshs_solve_dense_sens_out): the outputs and d(out)/dp_j of every parameter at
+        t_eval.  States and state sensitivities stay on the device — one more launch maps them to the outputs, and only those are copied back (want_states=True returns
+        them too).  The solver must have been created with sens=True on a DiffSL model with inputs and an out_i; models without a device-resident integrator with
+        sensitivities (DAEs) are stepped host-driven (group / deterministic_pow unused).
+        Returns (out [nt, nbatch, nout], dout [nparams, nt, nbatch, nout], totals dict[, y [nt, nbatch, n], sens [nparams, nt, nbatch, n]][, member dict(stats, status)])."""
+        te = np.ascontiguousarray(t_eval, dtype=np.float64)
+        npar = int(self._L.dshs_nparams(self._h))
+        nout = int(getattr(getattr(self, "_jit_model", None), "nout", 0))
+        out = np.empty((te.size, self.nbatch, max(nout, 1)))
+        dout = np.empty((npar, te.size, self.nbatch, max(nout, 1)))
+        y = np.empty((te.size, self.nbatch, self.n)) if want_states else None
+        sens = np.empty((npar, te.size, self.nbatch, self.n)) if want_states else None
+        totals = (C.c_int64 * 6)()
+        m = dict(stats=np.empty((5, self.nbatch), dtype=np.int32), status=np.empty(self.nbatch, dtype=np.int32)) if want_member_stats else None
+        i32 = lambda a: a.ctypes.data_as(_ffi.c_i32p)
+        dp = lambda a: a.ctypes.data_as(_ffi.c_dp) if a is not None else None
+        check(self._L.dshs_solve_dense_sens_out(self._h, dp(te), te.size, int(group), int(deterministic_pow), dp(y), dp(sens), dp(out), dp(dout),
+                                                i32(m["stats"]) if m else None, i32(m["status"]) if m else None, totals), host=True)
+        ret = (out, dout, dict(zip(self.ADAPTIVE_TOTALS, [int(v) for v in totals])))
+        if want_states:
+            ret += (y, sens)
+        if want_member_stats:
+            ret += (m,)
+        return ret
+
 
 class OdeBuilder:
     """OdeBuilder (crates/diffsol/src/ode_solver/builder.rs:22-146): fluent problem description; `.bdf()` etc. create the solver."""

@@ -287,7 +287,7 @@ int dsh_lu_download(dsh_lu* lu, double* factors_host, int32_t* pivots_host);
  * works wherever a registry id does: dsh_model_*, the fused Newton kernels (static form), the device-resident integrators (static form), and the
  * host-side integrators of diffsol_hip_solver.h.  Kernel families are compiled on first use and cached on disk (DSH_JIT_CACHE=<dir> | off; default <package>/_jit_cache, keyed by the
  * translation unit, the options and the library's headers); dsh_model_precompile (family 0 operators, 1 fused Newton,
- * 2 resident BDF, 3 resident SDIRK) pays that cost up front and needs no GPU.  `model_size` arguments are ignored for these ids. */
+ * 2 resident BDF, 3 resident SDIRK, 4 output sensitivities) pays that cost up front and needs no GPU.  `model_size` arguments are ignored for these ids. */
 #define DSH_MODEL_JIT_BASE 1000
 #define DSH_JIT_FORM_STATIC 0
 #define DSH_JIT_FORM_DYNAMIC 1
@@ -318,6 +318,22 @@ int dsh_model_set_band(int model_id, int jac_kl, int jac_ku, int mass_kl, int ma
 int dsh_model_band(int model, int64_t size, int* jac_kl, int* jac_ku, int* mass_kl, int* mass_ku);
 /* out_i of a run-time-compiled model (DiffSl::out, calc_out): out is nout x nbatch, batch-fastest */
 int dsh_model_out(dsh_ctx* ctx, int model, int64_t size, int64_t nbatch, double t, const double* x, const double* p, double* out);
+/* Output sensitivities (the reference's solve_dense_sensitivities for a model with an out_i, ode_solver/sensitivities.rs:360-397: per save point and parameter j
+ * out.jac_mul(y, s_j) + out.sens_mul(y, e_j)): out_i and d(out_i)/dp_j at every save point of every member from ONE launch (csrc/dsh_out_sens_kernel.hpp).
+ * dsh_model_set_out_sens_source registers the source dshs_diffsl_generate makes for DSHS_DIFFSL_HIP_OUT_SENS with a run-time-compiled model (same n and nparams,
+ * nout >= 1); it is a module of its own, compiled at the first dsh_model_out_sens and cached like the others.  dsh_model_has_out_sens: 1 if one is registered.
+ * All pointers are device pointers except t_cols_host [ncols].  Batch-fastest layouts: y [ncols][n][nb], sens [nparams][ncols][n][nb], p [nparams][nb],
+ * out [ncols][nout][nb], dout [nparams][ncols][nout][nb].  member_cols (may be NULL): int32 [nb], the number of columns member b produced — the others are written as
+ * NaN in out and dout and their inputs are not read.  DSH_E_UNSUPPORTED if the model has no registered source.
+ * dsh_model_out_sens_strided: the same with the sensitivities at sens[j * sens_param_stride + c * sens_col_stride + i * nb + b] (strides in doubles) — the
+ * device-resident integrators write [ncols][nparams][n][nb]. */
+int dsh_model_set_out_sens_source(int model_id, const char* source);
+int dsh_model_has_out_sens(int model_id);
+int dsh_model_out_sens_dims(int model_id, int64_t* nstates, int64_t* nparams, int64_t* nout);
+int dsh_model_out_sens(dsh_ctx* ctx, int model, int64_t nb, int64_t ncols, const double* t_cols_host, const double* y, const double* sens, const double* p,
+                       const int32_t* member_cols, double* out, double* dout);
+int dsh_model_out_sens_strided(dsh_ctx* ctx, int model, int64_t nb, int64_t ncols, const double* t_cols_host, const double* y, const double* sens,
+                               int64_t sens_param_stride, int64_t sens_col_stride, const double* p, const int32_t* member_cols, double* out, double* dout);
 
 int dsh_model_info(int model, int64_t size, int64_t* nstates, int64_t* nparams, int* has_mass, int64_t* nroots);
 int dsh_model_rhs(dsh_ctx* ctx, int model, int64_t size, int64_t nbatch, double t, const double* x, const double* p, double* y);

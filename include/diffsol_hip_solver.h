@@ -182,6 +182,17 @@ int dshs_solve_adaptive(dshs_solver* s, double t_final, int64_t max_cols, int gr
 int dshs_solve_dense_adaptive_sens(dshs_solver* s, const double* t_eval, int64_t nt, int group /* 1 | 64 */, int deterministic_pow, double* y_host,
                                    double* sens_host, int32_t* stats_host, int32_t* status_host, int64_t* totals);
 
+/* Output sensitivities: out_i and d(out_i)/dp_j at t_eval for a solver created with forward sensitivities (dshs_create_sens) on a DiffSL model with inputs and an
+ * out_i (dsh_model_set_out_sens_source) — what the reference's solve_dense_sensitivities returns for such a model (sensitivities.rs:360-397).  Where the model has a
+ * device-resident integrator with forward sensitivities (dshs_solve_dense_adaptive_sens) that launch runs, its states and sensitivities stay on the device, ONE more
+ * launch (dsh_model_out_sens) maps them to the outputs, and only out / dout are copied back (y_host / sens_host too when they are not NULL: [nt][b][state],
+ * [nparams][nt][b][state]).  Otherwise (DAEs, models without such an integrator) the host-driven solver is stepped and interpolated at the save points (group and
+ * deterministic_pow are not used) and the collected columns go through the same launch.  out_host: [nt][b][nout]; dout_host: [nparams][nt][b][nout].
+ * DSH_E_UNSUPPORTED: no sensitivities, no output-sensitivity source, Tsit45, a reset_i, a stop condition that fires before the last save point.
+ * stats_host / status_host / totals as dshs_solve_dense_adaptive (host-driven: the lock-step solver's counters for every member, status 0). */
+int dshs_solve_dense_sens_out(dshs_solver* s, const double* t_eval, int64_t nt, int group /* 1 | 64 */, int deterministic_pow, double* y_host, double* sens_host,
+                              double* out_host, double* dout_host, int32_t* stats_host, int32_t* status_host, int64_t* totals);
+
 /* ---- DiffSL front end: what OdeBuilder::build_from_diffsl does with the external `diffsl` compiler
  * (crates/diffsol/src/ode_solver/builder.rs, crates/diffsol/src/ode_equations/diffsl.rs): DiffSL text -> source code of the model.
  * target DSHS_DIFFSL_HIP_STATIC: `struct dsh::JitModel` (n <= 8, register-resident; feeds dsh_model_compile);
@@ -194,6 +205,12 @@ int dshs_solve_dense_adaptive_sens(dshs_solver* s, const double* t_eval, int64_t
 #define DSHS_DIFFSL_HIP_STATIC 0
 #define DSHS_DIFFSL_HIP_DYNAMIC 1
 #define DSHS_DIFFSL_HOST_C 2
+/* output sensitivities of a model with inputs and an out_i (an error otherwise, naming what is missing); the text generated for the three targets above does not
+ * depend on these.  DSHS_DIFFSL_HIP_OUT_SENS: jit_out_component / jit_out_jac_component / jit_out_sens_component over accessors (feeds
+ * dsh_model_set_out_sens_source); DSHS_DIFFSL_HOST_OUT_SENS: extern "C" dsl_dims, dsl_out(t, x, p, g), dsl_out_jac_mul(t, x, p, v, g) with v over the states,
+ * dsl_out_sens_mul(t, x, p, v, g) with v over the inputs — the CPU twin the tests check the kernel against. */
+#define DSHS_DIFFSL_HIP_OUT_SENS 3
+#define DSHS_DIFFSL_HOST_OUT_SENS 4
 int dshs_diffsl_generate(const char* code, int target, char** source_out, int64_t* dims, double* defaults_out, int64_t defaults_cap);
 void dshs_free_string(char* s);
 /* The reference's DiffSL model index (DiffSlContext::model_index, ode_equations/diffsl.rs:52,115,406-411; the scalar `N` of a DiffSL text, 0 unless

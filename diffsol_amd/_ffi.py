@@ -140,6 +140,7 @@ DEVICE_ABI = {
     "dsh_model_out_sens_dims": (cint, [cint, c_i64p, c_i64p, c_i64p]),
     "dsh_model_out_sens": (cint, [vp, cint, i64, i64, c_dp, vp, vp, vp, vp, vp, vp]),
     "dsh_model_out_sens_strided": (cint, [vp, cint, i64, i64, c_dp, vp, vp, i64, i64, vp, vp, vp, vp]),
+    "dsh_model_out_fit": (cint, [vp, cint, i64, i64, c_dp, vp, vp, i64, i64, vp, vp, vp, cint, vp, vp, vp, vp]),
     "dsh_model_compile": (cint, [C.c_char_p, cint, i64, i64, i64, i64, cint, c_ip]),
     "dsh_model_release": (cint, [cint]),
     "dsh_model_precompile": (cint, [cint, cint]),
@@ -253,6 +254,7 @@ HOST_ABI = {
     "dshs_diffsl_set_model_index": (cint, [cint]),
     "dshs_solve_dense_adaptive_sens": (cint, [vp, c_dp, i64, cint, cint, c_dp, c_dp, c_i32p, c_i32p, c_i64p]),
     "dshs_solve_dense_sens_out": (cint, [vp, c_dp, i64, cint, cint, c_dp, c_dp, c_dp, c_dp, c_i32p, c_i32p, c_i64p]),
+    "dshs_solve_dense_sens_fit": (cint, [vp, c_dp, i64, cint, cint, c_dp, cint, c_dp, c_dp, c_dp, c_dp, c_i32p, c_i32p, c_i64p]),
     "dshs_solve_dense_adaptive": (cint, [vp, c_dp, i64, cint, cint, c_dp, vp, c_i32p, c_i32p, c_dp, c_i32p, c_i32p, c_i64p]),
     "dshs_solve_adaptive": (cint, [vp, dbl, i64, cint, cint, c_dp, c_dp, c_i32p, c_i32p, c_i32p, c_dp, c_i32p, c_i64p]),
 }

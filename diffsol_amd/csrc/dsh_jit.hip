@@ -52,6 +52,9 @@ struct JitModelRec {
   std::string out_sens_source;
   std::unique_ptr<JitModule> out_sens_module;
   bool out_sens_failed = false;
+  // the fit objective (dsh_model_out_fit): the same source behind dsh_out_fit_kernel.hpp, a third module of its own, compiled at the first request
+  std::unique_ptr<JitModule> out_fit_module;
+  bool out_fit_failed = false;
 };
 
 std::mutex g_mu;
@@ -362,6 +365,23 @@ int ensure_out_sens_module(JitModelRec* rec) {
   return DSH_OK;
 }
 
+// the fit-objective module of a model (registry lock held): <registered output-sensitivity source> + dsh_out_fit_kernel.hpp, compiled once.  k_out_fit_gn is part of
+// it only for models with at most kOutFitGnMaxNp parameters (its np (np + 1) / 2 accumulators are registers)
+constexpr int64_t kOutFitGnMaxNp = 8;
+int ensure_out_fit_module(JitModelRec* rec) {
+  if (rec->out_fit_module) return DSH_OK;
+  if (rec->out_sens_source.empty()) { set_error("the model has no output-sensitivity source (dsh_model_set_out_sens_source)"); return DSH_E_UNSUPPORTED; }
+  auto m = std::make_unique<JitModule>();
+  const std::string tu = std::string("#include <hip/hip_runtime.h>\n#include \"diffsol_detpow.h\"\n") + (rec->info.np <= kOutFitGnMaxNp ? "#define DSH_OUT_FIT_GN 1\n" : "") +
+                         rec->out_sens_source + "\n#include \"dsh_out_fit_kernel.hpp\"\n";
+  const std::vector<std::string> none;
+  record_request(tu, "dsh_out_fit_kernel.hpp", none);
+  const int rc = compile_tu(*rec, tu, "dsh_out_fit_kernel.hpp", none, m.get());
+  if (rc != DSH_OK) { rec->out_fit_failed = true; return rc; }
+  rec->out_fit_module = std::move(m);
+  return DSH_OK;
+}
+
 const char* ops_header(int form) { return form == DSH_JIT_FORM_STATIC ? "dsh_model_kernels.hpp" : "dsh_jit_dyn_kernels.hpp"; }
 
 }  // namespace
@@ -583,6 +603,9 @@ int dsh_model_set_out_sens_source(int model_id, const char* source) {
   if (rec->out_sens_module && rec->out_sens_module->module) (void)hipModuleUnload(rec->out_sens_module->module);
   rec->out_sens_module.reset();
   rec->out_sens_failed = false;
+  if (rec->out_fit_module && rec->out_fit_module->module) (void)hipModuleUnload(rec->out_fit_module->module);
+  rec->out_fit_module.reset();
+  rec->out_fit_failed = false;
   // the stated dimensions must be the ones the source was generated with
   rec->out_sens_source = std::string(source) + "\nstatic_assert(dsh::kOutSensN == " + std::to_string(rec->info.n) + " && dsh::kOutSensNP == " + std::to_string(rec->info.np) +
                          " && dsh::kOutSensNOut == " + std::to_string(rec->info.nout) + ", \"dsh_model_set_out_sens_source: dimensions do not match the model\");\n";
@@ -661,6 +684,65 @@ int dsh_model_out_sens(dsh_ctx* ctx, int model, int64_t nb, int64_t ncols, const
   return dsh_model_out_sens_strided(ctx, model, nb, ncols, t_cols_host, y, sens, ncols * n * nb, n * nb, p, member_cols, out, dout);
 }
 
+// ---- fit objective: per member the weighted sum of squares of (out - data), its gradient and the Gauss-Newton matrix from one launch (dsh_out_fit_kernel.hpp)
+int dsh_model_out_fit(dsh_ctx* ctx, int model, int64_t nb, int64_t ncols, const double* t_cols_host, const double* y, const double* sens, int64_t sens_param_stride,
+                      int64_t sens_col_stride, const double* p, const int32_t* member_cols, const double* data, int data_per_member, const double* weights, double* loss,
+                      double* grad, double* gn) {
+  DSH_ENTER(ctx);
+  DSH_REQUIRE(ctx != nullptr, "ctx is null");
+  DSH_REQUIRE(nb >= 1 && ncols >= 1, "at least one member and one column are needed");
+  DSH_REQUIRE(t_cols_host && y && sens && p && data && loss && grad, "null argument (only member_cols, weights and gn may be NULL)");
+  if (!dsh_model_has_out_sens(model)) {
+    set_error("dsh_model_out_fit: the model has no output-sensitivity source (a DiffSL model with inputs and an out_i registers one: dsh_model_set_out_sens_source)");
+    return DSH_E_UNSUPPORTED;
+  }
+  hipFunction_t f = nullptr;
+  int64_t n = 0;
+  const char* name = gn ? "k_out_fit_gn" : "k_out_fit";
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    JitModelRec* rec = find_model(model);
+    if (!rec) { set_error("dsh_model_out_fit: unknown model id"); return DSH_E_INVALID; }
+    if (gn && rec->info.np > kOutFitGnMaxNp) {
+      set_error("dsh_model_out_fit: the Gauss-Newton matrix is kept in registers, for models with at most " + std::to_string(kOutFitGnMaxNp) + " parameters; this one has " +
+                std::to_string(rec->info.np) + " (pass gn = NULL for the loss and its gradient)");
+      return DSH_E_UNSUPPORTED;
+    }
+    if (rec->out_fit_failed) { set_error("dsh_model_out_fit: the output-sensitivity source of this model did not compile behind the fit kernel"); return DSH_E_INVALID; }
+    n = rec->info.n;
+    const int crc = ensure_out_fit_module(rec);  // first request: compile (or load from the on-disk cache)
+    if (crc != DSH_OK) return crc;
+    JitModule& m = *rec->out_fit_module;
+    if (!m.module) DSH_HIP_CHECK(hipModuleLoadData(&m.module, m.code.data()));
+    auto it = m.functions.find(name);
+    if (it == m.functions.end()) {
+      hipFunction_t fn = nullptr;
+      DSH_HIP_CHECK(hipModuleGetFunction(&fn, m.module, name));
+      it = m.functions.emplace(name, fn).first;
+    }
+    f = it->second;
+  }
+  DSH_REQUIRE(sens_param_stride >= 0 && sens_col_stride >= n * nb, "the sensitivity strides must leave room for one n x nbatch block per column");
+  double* t_dev = nullptr;
+  int rc = dsh_malloc(ctx, (int64_t)sizeof(double) * ncols, 0, (void**)&t_dev);
+  if (rc != DSH_OK) return rc;
+  struct Release { dsh_ctx* c; void* q; ~Release() { dsh_free(c, q); } } release{ctx, t_dev};
+  DSH_HIP_CHECK(hipMemcpyAsync(t_dev, t_cols_host, sizeof(double) * (size_t)ncols, hipMemcpyHostToDevice, ctx->stream));
+  const unsigned block = 256;
+  const unsigned grid = (unsigned)((nb + block - 1) / block);
+  long long nb_ = nb, ncols_ = ncols, sj = sens_param_stride, sc = sens_col_stride;
+  const double* t_c = t_dev;
+  int per_member = data_per_member ? 1 : 0;
+  void* argv[] = {&nb_, &ncols_, &t_c, &y, &sens, &sj, &sc, &p, &member_cols, &data, &per_member, &weights, &loss, &grad, &gn};  // k_out_fit takes all but the last
+  rc = timed_call(ctx, 0, [&]() -> int {
+    DSH_HIP_CHECK(hipModuleLaunchKernel(f, grid, 1, 1, block, 1, 1, 0, ctx->stream, argv, nullptr));
+    return DSH_OK;
+  });
+  if (rc != DSH_OK) return rc;
+  DSH_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // t_cols_host is the caller's: it may go away when this returns
+  return DSH_OK;
+}
+
 int dsh_model_release(int model_id) {
   {
     int tw = -1;
@@ -677,11 +759,12 @@ int dsh_model_release(int model_id) {
   for (auto& kv : it->second->modules)
     if (kv.second && kv.second->module) (void)hipModuleUnload(kv.second->module);
   if (it->second->out_sens_module && it->second->out_sens_module->module) (void)hipModuleUnload(it->second->out_sens_module->module);
+  if (it->second->out_fit_module && it->second->out_fit_module->module) (void)hipModuleUnload(it->second->out_fit_module->module);
   g_models.erase(it);
   return DSH_OK;
 }
 
-// compile (not load) one kernel family of a run-time-compiled model: 0 operators, 1 fused Newton kernels, 2 resident BDF, 3 resident SDIRK, 4 output sensitivities.
+// compile (not load) one kernel family of a run-time-compiled model: 0 operators, 1 fused Newton kernels, 2 resident BDF, 3 resident SDIRK, 4 output sensitivities, 5 fit objective.
 // Needs no GPU; used by the build check and by callers that want to pay the compilation before the first solve.
 int64_t dsh_jit_compile_count(void) { return (int64_t)g_jit_compiles.load(); }
 
@@ -735,6 +818,7 @@ int dsh_model_precompile(int model_id, int family) {
   JitModelRec* rec = find_model(model_id);
   if (!rec) { set_error("dsh_model_precompile: unknown model id"); return DSH_E_INVALID; }
   if (family == 4) return ensure_out_sens_module(rec);  // output sensitivities (dsh_model_out_sens), any form
+  if (family == 5) return ensure_out_fit_module(rec);   // fit objective (dsh_model_out_fit), any form
   struct Unit { const char* header; std::string key; std::vector<std::string> group; };
   std::vector<Unit> units;
   const bool st = rec->info.form == DSH_JIT_FORM_STATIC;

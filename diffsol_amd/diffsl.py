@@ -17,7 +17,7 @@ TARGET_HIP_STATIC, TARGET_HIP_DYNAMIC, TARGET_HOST_C = 0, 1, 2
 # output sensitivities (models with inputs and an out_i): the device source of csrc/dsh_out_sens_kernel.hpp and its extern "C" CPU twin
 TARGET_HIP_OUT_SENS, TARGET_HOST_OUT_SENS = 3, 4
 FORM_STATIC, FORM_DYNAMIC, FORM_STATIC_BANDED = 0, 1, 2
-FAMILY_OPERATORS, FAMILY_FUSED, FAMILY_RESIDENT_BDF, FAMILY_RESIDENT_SDIRK, FAMILY_OUT_SENS = 0, 1, 2, 3, 4
+FAMILY_OPERATORS, FAMILY_FUSED, FAMILY_RESIDENT_BDF, FAMILY_RESIDENT_SDIRK, FAMILY_OUT_SENS, FAMILY_OUT_FIT = 0, 1, 2, 3, 4, 5
 
 
 def generate(code, target, model_index=0):

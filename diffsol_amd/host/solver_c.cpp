@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 
 #include "bdf.hpp"
@@ -311,15 +312,75 @@ dsh_adaptive_options adaptive_options_of(const dshs_solver* s, int group, int de
 }
 
 // dshs_solve_dense_sens_out: the outputs and their sensitivities computed on the device from the states and sensitivities of the launch (dsh_model_out_sens)
+// dshs_solve_dense_sens_fit: the same columns reduced against data to a least-squares objective per member (dsh_model_out_fit); out and dout are never stored
+struct OutFitSpec {
+  const double* data_host = nullptr;     // [nt][nout], or [nt][b][nout] if data_per_member
+  int data_per_member = 0;
+  const double* weights_host = nullptr;  // [nt][nout] or NULL
+  double* loss_host = nullptr;           // [b]
+  double* grad_host = nullptr;           // [b][nparams]
+  double* gn_host = nullptr;             // [b][nparams][nparams] or NULL
+};
 struct OutSensSpec {
   int model = 0;       // the model that carries the output-sensitivity source
   int64_t nout = 0;
   double* out_host = nullptr;   // [nt][b][nout]
   double* dout_host = nullptr;  // [nparams][nt][b][nout]
+  const OutFitSpec* fit = nullptr;  // set: the fit objective instead of out / dout
+  const char* fn = "dshs_solve_dense_sens_out";  // the entry point the messages name
 };
 // device [col][k][b] blocks -> host [col][b][k], block by block (the blocks of dout, [j][col], are in the same order on both sides)
 void download_blocks(dsh_ctx* c, int64_t nblocks, int64_t rows, int64_t nb, const double* dev, double* host) {
   for (int64_t k = 0; k < nblocks; ++k) check(dsh_vec_download(c, rows, nb, dev + (size_t)(k * rows * nb), host + (size_t)(k * rows * nb)), "output sensitivities download");
+}
+
+// What both routes of dshs_solve_dense_sens_out / dshs_solve_dense_sens_fit do with the columns they left on the device — y [col][state][b], the sensitivity of parameter
+// j and column c at sens_dev + j * sens_sj + c * sens_sc, members in the caller's order: ONE launch, and only its results travel.
+void map_outputs(dshs_solver* s, const OutSensSpec& os, const double* t_eval, int64_t nt, const double* y_dev, const double* sens_dev, int64_t sens_sj, int64_t sens_sc) {
+  dsh_ctx* c = s->ctx.raw();
+  const int64_t nb = s->ctx.nbatch(), npar = s->problem.eqn->nparams(), nout = os.nout;
+  const double* params = s->problem.eqn->params().ptr();
+  void *a_dev = nullptr, *b_dev = nullptr, *c_dev = nullptr;
+  struct Release {
+    dsh_ctx* c; std::vector<void**> bufs;
+    ~Release() { for (void** q : bufs) if (*q) dsh_free(c, *q); }
+  } release{c, {&a_dev, &b_dev, &c_dev}};
+  if (!os.fit) {
+    check(dsh_malloc(c, (int64_t)sizeof(double) * nt * nout * nb, 0, &a_dev), "output sensitivities (out)");
+    check(dsh_malloc(c, (int64_t)sizeof(double) * npar * nt * nout * nb, 0, &b_dev), "output sensitivities (dout)");
+    check(dsh_model_out_sens_strided(c, os.model, nb, nt, t_eval, y_dev, sens_dev, sens_sj, sens_sc, params, nullptr, (double*)a_dev, (double*)b_dev), "dsh_model_out_sens");
+    download_blocks(c, nt, nout, nb, (const double*)a_dev, os.out_host);
+    download_blocks(c, npar * nt, nout, nb, (const double*)b_dev, os.dout_host);
+    return;
+  }
+  const OutFitSpec& f = *os.fit;
+  const int64_t nq = npar * (npar + 1) / 2, nres = 1 + npar + (f.gn_host ? nq : 0);
+  // data in the device layout: [col][output] as it is, [col][b][output] -> [col][output][b] column by column
+  check(dsh_malloc(c, (int64_t)sizeof(double) * nt * nout * (f.data_per_member ? nb : 1), 0, &a_dev), "fit data");
+  if (f.data_per_member)
+    for (int64_t k = 0; k < nt; ++k) check(dsh_vec_upload(c, nout, nb, f.data_host + (size_t)(k * nout * nb), (double*)a_dev + (size_t)(k * nout * nb)), "fit data upload");
+  else
+    check(dsh_h2d(c, a_dev, f.data_host, (int64_t)sizeof(double) * nt * nout), "fit data upload");
+  if (f.weights_host) {
+    check(dsh_malloc(c, (int64_t)sizeof(double) * nt * nout, 0, &b_dev), "fit weights");
+    check(dsh_h2d(c, b_dev, f.weights_host, (int64_t)sizeof(double) * nt * nout), "fit weights upload");
+  }
+  check(dsh_malloc(c, (int64_t)sizeof(double) * nres * nb, 0, &c_dev), "fit results");  // loss [b] | grad [j][b] | gn [q][b]
+  double *loss_dev = (double*)c_dev, *grad_dev = loss_dev + nb, *gn_dev = f.gn_host ? grad_dev + npar * nb : nullptr;
+  check(dsh_model_out_fit(c, os.model, nb, nt, t_eval, y_dev, sens_dev, sens_sj, sens_sc, params, nullptr, (const double*)a_dev, f.data_per_member, (const double*)b_dev,
+                          loss_dev, grad_dev, gn_dev), "dsh_model_out_fit");
+  check(dsh_d2h(c, f.loss_host, loss_dev, (int64_t)sizeof(double) * nb), "fit loss download");
+  check(dsh_vec_download(c, npar, nb, grad_dev, f.grad_host), "fit gradient download");
+  if (f.gn_host) {
+    std::vector<double> packed((size_t)(nq * nb));  // [b][q], the upper triangle row-major -> the full symmetric matrix
+    check(dsh_vec_download(c, nq, nb, gn_dev, packed.data()), "fit Gauss-Newton download");
+    for (int64_t b = 0; b < nb; ++b) {
+      const double* q = packed.data() + (size_t)(b * nq);
+      double* g = f.gn_host + (size_t)(b * npar * npar);
+      for (int64_t j = 0; j < npar; ++j)
+        for (int64_t l = j; l < npar; ++l, ++q) g[j * npar + l] = g[l * npar + j] = *q;
+    }
+  }
 }
 
 // lazy: status_host is fetched only when a member failed (totals[5] != 0; it is all zero otherwise) and root_idx_host only for models with root
@@ -348,11 +409,11 @@ void run_resident(dshs_solver* s, const double* t_eval, int64_t nt, int group, i
   // every device buffer of this call is released when the function leaves, also by the exceptions check() throws between the allocations (an out-of-memory on
   // the second output buffer is exactly when leaking the first one would hurt)
   void *tmp_out = nullptr, *sorted_out = nullptr, *stats_dev = nullptr, *status_dev = nullptr, *troot_dev = nullptr, *ridx_dev = nullptr, *ncols_dev = nullptr, *sens_dev = nullptr,
-       *sens_sorted = nullptr, *outs_dev = nullptr, *douts_dev = nullptr;
+       *sens_sorted = nullptr;
   struct Release {
     dsh_ctx* c; std::vector<void**> bufs;
     ~Release() { for (void** q : bufs) if (*q) dsh_free(c, *q); }
-  } release{c, {&tmp_out, &sorted_out, &stats_dev, &status_dev, &troot_dev, &ridx_dev, &ncols_dev, &sens_dev, &sens_sorted, &outs_dev, &douts_dev}};
+  } release{c, {&tmp_out, &sorted_out, &stats_dev, &status_dev, &troot_dev, &ridx_dev, &ncols_dev, &sens_dev, &sens_sorted}};
   if (!out) { check(dsh_malloc(c, (int64_t)sizeof(double) * nt * n * nb, 0, &tmp_out), "adaptive out"); out = (double*)tmp_out; }
   double* user_out = out;
   if (sorted) { check(dsh_malloc(c, (int64_t)sizeof(double) * nt * n * nb, 0, &sorted_out), "adaptive out (sorted)"); out = (double*)sorted_out; }
@@ -421,14 +482,7 @@ void run_resident(dshs_solver* s, const double* t_eval, int64_t nt, int group, i
   if (rc == DSH_OK && out_sens) {
     // states (`out`, [col][state][b]) and sensitivities (sens_dev, [col][parameter][state][b]) are in the caller's member order by now and never left the device:
     // one launch maps them to the outputs and their sensitivities, and only those travel (a failed member's columns hold NaN and stay NaN through the arithmetic)
-    check(dsh_malloc(c, (int64_t)sizeof(double) * nt * out_sens->nout * nb, 0, &outs_dev), "output sensitivities (out)");
-    check(dsh_malloc(c, (int64_t)sizeof(double) * npar * nt * out_sens->nout * nb, 0, &douts_dev), "output sensitivities (dout)");
-    rc = dsh_model_out_sens_strided(c, out_sens->model, nb, nt, t_eval, out, (const double*)sens_dev, n * nb, npar * n * nb, s->problem.eqn->params().ptr(), nullptr,
-                                    (double*)outs_dev, (double*)douts_dev);
-    if (rc == DSH_OK) {
-      download_blocks(c, nt, out_sens->nout, nb, (const double*)outs_dev, out_sens->out_host);
-      download_blocks(c, npar * nt, out_sens->nout, nb, (const double*)douts_dev, out_sens->dout_host);
-    }
+    map_outputs(s, *out_sens, t_eval, nt, out, (const double*)sens_dev, n * nb, npar * n * nb);
   }
   if (rc == DSH_OK && y_host)
     for (int64_t k = 0; k < nt && rc == DSH_OK; ++k) rc = dsh_vec_download(c, n, nb, out + (size_t)(k * n * nb), y_host + (size_t)(k * n * nb));
@@ -902,85 +956,123 @@ int dshs_solve_dense_adaptive_sens(dshs_solver* s, const double* t_eval, int64_t
 // Output sensitivities (the reference's solve_dense_sensitivities for a model with an out_i, ode_solver/sensitivities.rs:360-397): the device-resident launch with forward
 // sensitivities where the model has one — its states and sensitivities stay on the device — else the host-driven solver stepped and interpolated at the save points;
 // either way ONE launch of k_out_sens (dsh_model_out_sens) maps every column, member and parameter, and only out / dout (and what the caller asks for besides) are copied.
+// The body is shared with dshs_solve_dense_sens_fit: `os` says what the launch after the solve computes and which entry point the messages name.
+static void solve_sens_outputs(dshs_solver* s, const double* t_eval, int64_t nt, int group, int deterministic_pow, double* y_host, double* sens_host, OutSensSpec& os,
+                               int32_t* stats_host, int32_t* status_host, int64_t* totals) {
+  const std::string fn = os.fn;
+  if (s->method == DSHS_METHOD_TSIT45) throw LaError(DSH_E_UNSUPPORTED, fn + ": Tsit45 has no forward sensitivities; use BDF, TR-BDF2 or ESDIRK34");
+  if (!s->problem.sens) throw LaError(DSH_E_UNSUPPORTED, fn + ": the solver was not created with forward sensitivities (dshs_create_sens)");
+  int64_t msize = 0, mn = 0, mnp = 0;
+  if (!s->problem.eqn->registry_model(&os.model, &msize) || !dsh_model_has_out_sens(os.model))
+    throw LaError(DSH_E_UNSUPPORTED, fn + ": the model has no output-sensitivity source — it needs a DiffSL model with inputs and an out_i "
+                                     "(dsh_model_set_out_sens_source); built-in registry models have no out_i");
+  check(dsh_model_out_sens_dims(os.model, &mn, &mnp, &os.nout), "dsh_model_out_sens_dims");
+  if (s->problem.eqn->has_reset()) throw LaError(DSH_E_UNSUPPORTED, fn + ": the model has a reset_i; sensitivities across resets are not supported");
+  const int64_t n = s->problem.eqn->nstates(), nb = s->ctx.nbatch(), npar = s->problem.eqn->nparams();
+  if (mn != n || mnp != npar) throw LaError(DSH_E_INVALID, fn + ": the output-sensitivity source does not belong to this model");
+  for (int64_t k = 0; k + 1 < nt; ++k) if (t_eval[k] > t_eval[k + 1]) throw LaError(DSH_E_INVALID, fn + ": t_eval must be increasing");
+  if (t_eval[0] < s->problem.t0) throw LaError(DSH_E_INVALID, fn + ": t_eval must not start before t0");
+  int64_t tot[6] = {0, 0, 0, 0, 0, 0};
+  s->resident_roots_valid = false;
+  if (pick_resident(s, group).ok) {
+    run_resident(s, t_eval, nt, group, deterministic_pow, y_host, nullptr, stats_host, status_host, nullptr, nullptr, nullptr, tot, false, sens_host, &os);
+    s->last_mode = group;
+  } else {
+    // host-driven: a fresh solver from (t0, y0), stepped to the last save point; states and sensitivities interpolated at every save point the step has passed
+    // (the loop of diffsol_ode_solve_fwd_sens, on device columns)
+    if (s->solver->get_statistics().number_of_steps != 0 || s->solver->t() != s->problem.t0) s->make_solver();
+    dsh_ctx* c = s->ctx.raw();
+    void *y_dev = nullptr, *sens_dev = nullptr;
+    struct Release {
+      dsh_ctx* c; std::vector<void**> bufs;
+      ~Release() { for (void** q : bufs) if (*q) dsh_free(c, *q); }
+    } release{c, {&y_dev, &sens_dev}};
+    const int64_t col_bytes = (int64_t)sizeof(double) * n * nb;
+    check(dsh_malloc(c, col_bytes * nt, 0, &y_dev), "sens_out states");
+    check(dsh_malloc(c, col_bytes * nt * npar, 0, &sens_dev), "sens_out sensitivities");  // [parameter][col][state][b]
+    int64_t col = 0;
+    std::vector<HipVec> sv;
+    auto drain = [&](double upto) {
+      while (col < nt && t_eval[col] <= upto) {
+        HipVec y = s->solver->interpolate(t_eval[col]);
+        check(dsh_d2d(c, (double*)y_dev + (size_t)(col * n * nb), y.ptr(), col_bytes), "sens_out d2d");
+        sv.clear();
+        if (s->bdf) s->bdf->interpolate_sens_inplace(t_eval[col], sv); else s->sdirk->interpolate_sens_inplace(t_eval[col], sv);
+        if ((int64_t)sv.size() != npar) throw LaError(DSH_E_INVALID, fn + ": the solver carries no sensitivities");
+        for (int64_t j = 0; j < npar; ++j) check(dsh_d2d(c, (double*)sens_dev + (size_t)((j * nt + col) * n * nb), sv[(size_t)j].ptr(), col_bytes), "sens_out d2d");
+        ++col;
+      }
+    };
+    drain(s->solver->t());
+    if (col < nt) {
+      s->solver->set_stop_time(t_eval[nt - 1]);
+      while (true) {
+        const OdeSolverStopReason r = s->solver->step();
+        if (r == OdeSolverStopReason::RootFound)
+          throw LaError(DSH_E_UNSUPPORTED, fn + ": a stop condition fired before the last save point; events with forward sensitivities are not supported");
+        drain(s->solver->t());
+        if (r == OdeSolverStopReason::TstopReached) break;
+      }
+    }
+    map_outputs(s, os, t_eval, nt, (const double*)y_dev, (const double*)sens_dev, nt * n * nb, n * nb);
+    if (y_host) download_blocks(c, nt, n, nb, (const double*)y_dev, y_host);
+    if (sens_host) download_blocks(c, npar * nt, n, nb, (const double*)sens_dev, sens_host);
+    const OdeSolverStatistics& st = s->solver->get_statistics();
+    const int64_t per[5] = {(int64_t)st.number_of_steps, (int64_t)st.number_of_nonlinear_solver_iterations, (int64_t)st.number_of_linear_solver_setups,
+                            (int64_t)st.number_of_error_test_failures, (int64_t)st.number_of_nonlinear_solver_fails};
+    for (int k = 0; k < 5; ++k) tot[k] = per[k] * nb;
+    if (stats_host) for (int k = 0; k < 5; ++k) for (int64_t b = 0; b < nb; ++b) stats_host[(size_t)(k * nb + b)] = (int32_t)per[k];
+    if (status_host) std::fill(status_host, status_host + nb, 0);
+    s->last_mode = DSHS_ENSEMBLE_LOCKSTEP;
+  }
+  for (int k = 0; k < 6; ++k) { s->last_totals[k] = tot[k]; if (totals) totals[k] = tot[k]; }
+}
+
 int dshs_solve_dense_sens_out(dshs_solver* s, const double* t_eval, int64_t nt, int group, int deterministic_pow, double* y_host, double* sens_host, double* out_host,
                               double* dout_host, int32_t* stats_host, int32_t* status_host, int64_t* totals) {
   return guarded_flushed(s, [&]() {
     if (!t_eval || nt < 1 || !out_host || !dout_host) throw LaError(DSH_E_INVALID, "dshs_solve_dense_sens_out: t_eval, out_host and dout_host are needed");
-    if (s->method == DSHS_METHOD_TSIT45) throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_dense_sens_out: Tsit45 has no forward sensitivities; use BDF, TR-BDF2 or ESDIRK34");
-    if (!s->problem.sens) throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_dense_sens_out: the solver was not created with forward sensitivities (dshs_create_sens)");
     OutSensSpec os;
-    int64_t msize = 0, mn = 0, mnp = 0;
-    if (!s->problem.eqn->registry_model(&os.model, &msize) || !dsh_model_has_out_sens(os.model))
-      throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_dense_sens_out: the model has no output-sensitivity source — it needs a DiffSL model with inputs and an out_i "
-                                       "(dsh_model_set_out_sens_source); built-in registry models have no out_i");
-    check(dsh_model_out_sens_dims(os.model, &mn, &mnp, &os.nout), "dsh_model_out_sens_dims");
-    if (s->problem.eqn->has_reset()) throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_dense_sens_out: the model has a reset_i; sensitivities across resets are not supported");
     os.out_host = out_host; os.dout_host = dout_host;
-    const int64_t n = s->problem.eqn->nstates(), nb = s->ctx.nbatch(), npar = s->problem.eqn->nparams();
-    if (mn != n || mnp != npar) throw LaError(DSH_E_INVALID, "dshs_solve_dense_sens_out: the output-sensitivity source does not belong to this model");
-    for (int64_t k = 0; k + 1 < nt; ++k) if (t_eval[k] > t_eval[k + 1]) throw LaError(DSH_E_INVALID, "dshs_solve_dense_sens_out: t_eval must be increasing");
-    if (t_eval[0] < s->problem.t0) throw LaError(DSH_E_INVALID, "dshs_solve_dense_sens_out: t_eval must not start before t0");
-    int64_t tot[6] = {0, 0, 0, 0, 0, 0};
-    s->resident_roots_valid = false;
-    if (pick_resident(s, group).ok) {
-      run_resident(s, t_eval, nt, group, deterministic_pow, y_host, nullptr, stats_host, status_host, nullptr, nullptr, nullptr, tot, false, sens_host, &os);
-      s->last_mode = group;
-    } else {
-      // host-driven: a fresh solver from (t0, y0), stepped to the last save point; states and sensitivities interpolated at every save point the step has passed
-      // (the loop of diffsol_ode_solve_fwd_sens, on device columns)
-      if (s->solver->get_statistics().number_of_steps != 0 || s->solver->t() != s->problem.t0) s->make_solver();
-      dsh_ctx* c = s->ctx.raw();
-      void *y_dev = nullptr, *sens_dev = nullptr, *outs_dev = nullptr, *douts_dev = nullptr;
-      struct Release {
-        dsh_ctx* c; std::vector<void**> bufs;
-        ~Release() { for (void** q : bufs) if (*q) dsh_free(c, *q); }
-      } release{c, {&y_dev, &sens_dev, &outs_dev, &douts_dev}};
-      const int64_t col_bytes = (int64_t)sizeof(double) * n * nb;
-      check(dsh_malloc(c, col_bytes * nt, 0, &y_dev), "sens_out states");
-      check(dsh_malloc(c, col_bytes * nt * npar, 0, &sens_dev), "sens_out sensitivities");  // [parameter][col][state][b]
-      check(dsh_malloc(c, (int64_t)sizeof(double) * nt * os.nout * nb, 0, &outs_dev), "sens_out out");
-      check(dsh_malloc(c, (int64_t)sizeof(double) * npar * nt * os.nout * nb, 0, &douts_dev), "sens_out dout");
-      int64_t col = 0;
-      std::vector<HipVec> sv;
-      auto drain = [&](double upto) {
-        while (col < nt && t_eval[col] <= upto) {
-          HipVec y = s->solver->interpolate(t_eval[col]);
-          check(dsh_d2d(c, (double*)y_dev + (size_t)(col * n * nb), y.ptr(), col_bytes), "sens_out d2d");
-          sv.clear();
-          if (s->bdf) s->bdf->interpolate_sens_inplace(t_eval[col], sv); else s->sdirk->interpolate_sens_inplace(t_eval[col], sv);
-          if ((int64_t)sv.size() != npar) throw LaError(DSH_E_INVALID, "dshs_solve_dense_sens_out: the solver carries no sensitivities");
-          for (int64_t j = 0; j < npar; ++j) check(dsh_d2d(c, (double*)sens_dev + (size_t)((j * nt + col) * n * nb), sv[(size_t)j].ptr(), col_bytes), "sens_out d2d");
-          ++col;
-        }
-      };
-      drain(s->solver->t());
-      if (col < nt) {
-        s->solver->set_stop_time(t_eval[nt - 1]);
-        while (true) {
-          const OdeSolverStopReason r = s->solver->step();
-          if (r == OdeSolverStopReason::RootFound)
-            throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_dense_sens_out: a stop condition fired before the last save point; events with forward sensitivities are not supported");
-          drain(s->solver->t());
-          if (r == OdeSolverStopReason::TstopReached) break;
-        }
-      }
-      check(dsh_model_out_sens(c, os.model, nb, nt, t_eval, (const double*)y_dev, (const double*)sens_dev, s->problem.eqn->params().ptr(), nullptr, (double*)outs_dev,
-                               (double*)douts_dev), "dsh_model_out_sens");
-      download_blocks(c, nt, os.nout, nb, (const double*)outs_dev, out_host);
-      download_blocks(c, npar * nt, os.nout, nb, (const double*)douts_dev, dout_host);
-      if (y_host) download_blocks(c, nt, n, nb, (const double*)y_dev, y_host);
-      if (sens_host) download_blocks(c, npar * nt, n, nb, (const double*)sens_dev, sens_host);
-      const OdeSolverStatistics& st = s->solver->get_statistics();
-      const int64_t per[5] = {(int64_t)st.number_of_steps, (int64_t)st.number_of_nonlinear_solver_iterations, (int64_t)st.number_of_linear_solver_setups,
-                              (int64_t)st.number_of_error_test_failures, (int64_t)st.number_of_nonlinear_solver_fails};
-      for (int k = 0; k < 5; ++k) tot[k] = per[k] * nb;
-      if (stats_host) for (int k = 0; k < 5; ++k) for (int64_t b = 0; b < nb; ++b) stats_host[(size_t)(k * nb + b)] = (int32_t)per[k];
-      if (status_host) std::fill(status_host, status_host + nb, 0);
-      s->last_mode = DSHS_ENSEMBLE_LOCKSTEP;
-    }
-    for (int k = 0; k < 6; ++k) { s->last_totals[k] = tot[k]; if (totals) totals[k] = tot[k]; }
+    solve_sens_outputs(s, t_eval, nt, group, deterministic_pow, y_host, sens_host, os, stats_host, status_host, totals);
     return 0;
   });
 }
+
+// One iteration of a least-squares fit: the same solve, then ONE launch of k_out_fit / k_out_fit_gn (dsh_model_out_fit) reduces the outputs and their sensitivities
+// against the data per member.  No out / dout buffer exists on either side; loss, gradient and the Gauss-Newton matrix are all that is copied back.
+int dshs_solve_dense_sens_fit(dshs_solver* s, const double* t_eval, int64_t nt, int group, int deterministic_pow, const double* data_host, int data_per_member,
+                              const double* weights_host, double* loss_host, double* grad_host, double* gn_host, int32_t* stats_host, int32_t* status_host, int64_t* totals) {
+  return guarded_flushed(s, [&]() {
+    if (!t_eval || nt < 1 || !data_host || !loss_host || !grad_host)
+      throw LaError(DSH_E_INVALID, "dshs_solve_dense_sens_fit: t_eval, data_host, loss_host and grad_host are needed");
+    OutFitSpec fit;
+    fit.data_host = data_host; fit.data_per_member = data_per_member ? 1 : 0; fit.weights_host = weights_host;
+    fit.loss_host = loss_host; fit.grad_host = grad_host; fit.gn_host = gn_host;
+    OutSensSpec os;
+    os.fit = &fit; os.fn = "dshs_solve_dense_sens_fit";
+    const int64_t nb = s->ctx.nbatch(), npar = s->problem.eqn->nparams();
+    if (gn_host && npar > 8)
+      throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_dense_sens_fit: the Gauss-Newton matrix is accumulated in registers, for models with at most 8 parameters; this one has " +
+                                       std::to_string(npar) + " (gn_host = NULL returns the loss and its gradient)");
+    std::vector<int32_t> status_local;  // the status decides which members get NaN: needed also when the caller does not ask for it
+    if (!status_host) { status_local.assign((size_t)nb, 0); status_host = status_local.data(); }
+    int64_t tot[6] = {0, 0, 0, 0, 0, 0};
+    solve_sens_outputs(s, t_eval, nt, group, deterministic_pow, nullptr, nullptr, os, stats_host, status_host, tot);
+    if (totals) for (int k = 0; k < 6; ++k) totals[k] = tot[k];
+    if (tot[5] != 0) {
+      // a failed member's columns hold NaN behind the point of failure, but a missing observation there would hide that: its results are NaN whatever the data say
+      const double nan = std::numeric_limits<double>::quiet_NaN();
+      for (int64_t b = 0; b < nb; ++b) {
+        if (status_host[b] == 0) continue;
+        loss_host[b] = nan;
+        std::fill(grad_host + (size_t)(b * npar), grad_host + (size_t)((b + 1) * npar), nan);
+        if (gn_host) std::fill(gn_host + (size_t)(b * npar * npar), gn_host + (size_t)((b + 1) * npar * npar), nan);
+      }
+    }
+    return 0;
+  });
+}
+
 
 }  // extern "C"

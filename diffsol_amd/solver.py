@@ -308,6 +308,42 @@ class Solver:
             ret += (m,)
         return ret
 
+    def solve_dense_sens_fit(self, t_eval, data, weights=None, gauss_newton=False, group=1, deterministic_pow=True, want_member_stats=False):
+        """One iteration of a least-squares fit on the device (dshs_solve_dense_sens_fit): the solve of solve_dense_sens_outputs, then one launch reduces the outputs
+        and their sensitivities against `data` per member — loss = sum w (out - data)^2, grad = 2 sum w (out - data) dout/dp and, with gauss_newton=True (models with
+        at most 8 parameters), gn = 2 sum w (dout/dp)(dout/dp)^T.  out and dout are stored nowhere; only these results are copied back.
+        data: [nt, nout] shared by all members, or [nt, nbatch, nout] per member; NaN marks a missing observation.  weights: [nt, nout] or None.  A member whose
+        integration failed gets NaN.
+        Returns (loss [nbatch], grad [nbatch, nparams], totals dict[, gn [nbatch, nparams, nparams]][, member dict(stats, status)])."""
+        te = np.ascontiguousarray(t_eval, dtype=np.float64)
+        npar = int(self._L.dshs_nparams(self._h))
+        nout = int(getattr(getattr(self, "_jit_model", None), "nout", 0))
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        if nout > 0 and data.shape not in ((te.size, nout), (te.size, self.nbatch, nout)):
+            raise ValueError(f"data must have shape (nt, nout) = {(te.size, nout)} or (nt, nbatch, nout) = {(te.size, self.nbatch, nout)}, not {data.shape}")
+        if nout == 0 and data.ndim not in (2, 3):
+            raise ValueError(f"data must have shape (nt, nout) or (nt, nbatch, nout), not {data.shape}")
+        # (nt, nout) and (nt, nbatch, nout) cannot be confused: they differ in the number of axes
+        per_member = data.ndim == 3
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.float64)
+            if weights.shape != (te.size, data.shape[-1]):
+                raise ValueError(f"weights must have shape (nt, nout) = {(te.size, data.shape[-1])}, not {weights.shape}")
+        loss, grad = np.empty(self.nbatch), np.empty((self.nbatch, npar))
+        gn = np.empty((self.nbatch, npar, npar)) if gauss_newton else None
+        totals = (C.c_int64 * 6)()
+        m = dict(stats=np.empty((5, self.nbatch), dtype=np.int32), status=np.empty(self.nbatch, dtype=np.int32)) if want_member_stats else None
+        i32 = lambda a: a.ctypes.data_as(_ffi.c_i32p)
+        dp = lambda a: a.ctypes.data_as(_ffi.c_dp) if a is not None else None
+        check(self._L.dshs_solve_dense_sens_fit(self._h, dp(te), te.size, int(group), int(deterministic_pow), dp(data), int(per_member), dp(weights), dp(loss), dp(grad),
+                                                dp(gn), i32(m["stats"]) if m else None, i32(m["status"]) if m else None, totals), host=True)
+        ret = (loss, grad, dict(zip(self.ADAPTIVE_TOTALS, [int(v) for v in totals])))
+        if gauss_newton:
+            ret += (gn,)
+        if want_member_stats:
+            ret += (m,)
+        return ret
+
 
 class OdeBuilder:
     """OdeBuilder (crates/diffsol/src/ode_solver/builder.rs:22-146): fluent problem description; `.bdf()` etc. create the solver."""

@@ -287,7 +287,7 @@ int dsh_lu_download(dsh_lu* lu, double* factors_host, int32_t* pivots_host);
  * works wherever a registry id does: dsh_model_*, the fused Newton kernels (static form), the device-resident integrators (static form), and the
  * host-side integrators of diffsol_hip_solver.h.  Kernel families are compiled on first use and cached on disk (DSH_JIT_CACHE=<dir> | off; default <package>/_jit_cache, keyed by the
  * translation unit, the options and the library's headers); dsh_model_precompile (family 0 operators, 1 fused Newton,
- * 2 resident BDF, 3 resident SDIRK, 4 output sensitivities) pays that cost up front and needs no GPU.  `model_size` arguments are ignored for these ids. */
+ * 2 resident BDF, 3 resident SDIRK, 4 output sensitivities, 5 fit objective) pays that cost up front and needs no GPU.  `model_size` arguments are ignored for these ids. */
 #define DSH_MODEL_JIT_BASE 1000
 #define DSH_JIT_FORM_STATIC 0
 #define DSH_JIT_FORM_DYNAMIC 1
@@ -334,6 +334,18 @@ int dsh_model_out_sens(dsh_ctx* ctx, int model, int64_t nb, int64_t ncols, const
                        const int32_t* member_cols, double* out, double* dout);
 int dsh_model_out_sens_strided(dsh_ctx* ctx, int model, int64_t nb, int64_t ncols, const double* t_cols_host, const double* y, const double* sens,
                                int64_t sens_param_stride, int64_t sens_col_stride, const double* p, const int32_t* member_cols, double* out, double* dout);
+/* Least-squares fit objective of every member from ONE launch (csrc/dsh_out_fit_kernel.hpp), on the inputs of dsh_model_out_sens_strided: out and dout are never stored.
+ *   loss [nb]            = sum over (c, k) of w (out - data)^2
+ *   grad [nparams][nb]   = 2 sum w (out - data) dout/dp_j
+ *   gn   [nparams (nparams + 1) / 2][nb] = 2 sum w dout/dp_j dout/dp_l, the upper triangle packed row-major ((0,0), (0,1), .., (1,1), ..); NULL: not computed.
+ * data: [ncols][nout] shared by all members (data_per_member == 0) or [ncols][nout][nb]; a NaN entry is a missing observation and contributes nothing.
+ * weights: [ncols][nout], or NULL for 1.  member_cols as above: a member with fewer than ncols columns gets NaN in all of its results.  The summation order (columns,
+ * then outputs, one member per thread) and every operation are fixed — see the header of the kernel — so a CPU restatement repeats the results bit for bit.
+ * A module of its own per model, compiled at the first call and cached (dsh_model_precompile family 5).  DSH_E_UNSUPPORTED: no registered output-sensitivity source;
+ * gn != NULL for a model with more than 8 parameters (the matrix is accumulated in registers).  DSH_E_INVALID: nb < 1, ncols < 1, a NULL required pointer. */
+int dsh_model_out_fit(dsh_ctx* ctx, int model, int64_t nb, int64_t ncols, const double* t_cols_host, const double* y, const double* sens, int64_t sens_param_stride,
+                      int64_t sens_col_stride, const double* p, const int32_t* member_cols, const double* data, int data_per_member, const double* weights, double* loss,
+                      double* grad, double* gn);
 
 int dsh_model_info(int model, int64_t size, int64_t* nstates, int64_t* nparams, int* has_mass, int64_t* nroots);
 int dsh_model_rhs(dsh_ctx* ctx, int model, int64_t size, int64_t nbatch, double t, const double* x, const double* p, double* y);

@@ -193,6 +193,15 @@ int dshs_solve_dense_adaptive_sens(dshs_solver* s, const double* t_eval, int64_t
 int dshs_solve_dense_sens_out(dshs_solver* s, const double* t_eval, int64_t nt, int group /* 1 | 64 */, int deterministic_pow, double* y_host, double* sens_host,
                               double* out_host, double* dout_host, int32_t* stats_host, int32_t* status_host, int64_t* totals);
 
+/* One iteration of a least-squares fit on the device: the solve of dshs_solve_dense_sens_out (same routes, same refusals), followed by ONE launch that reduces the
+ * outputs and their sensitivities against data to, per member, loss = sum w (out - data)^2, its gradient 2 sum w (out - data) dout/dp and — gn_host != NULL, models
+ * with at most 8 parameters — the Gauss-Newton matrix 2 sum w (dout/dp)(dout/dp)^T (dsh_model_out_fit).  Neither out nor dout is allocated anywhere; only the
+ * results below are copied back.  data_host: [nt][nout] shared by all members, or [nt][b][nout] (data_per_member != 0: the layout of out_host above); NaN marks a
+ * missing observation.  weights_host: [nt][nout] or NULL.  loss_host [b]; grad_host [b][nparams]; gn_host [b][nparams][nparams], full and symmetric.  A member whose
+ * integration status is non-zero gets NaN in all three.  stats_host / status_host / totals as dshs_solve_dense_sens_out. */
+int dshs_solve_dense_sens_fit(dshs_solver* s, const double* t_eval, int64_t nt, int group /* 1 | 64 */, int deterministic_pow, const double* data_host, int data_per_member,
+                              const double* weights_host, double* loss_host, double* grad_host, double* gn_host, int32_t* stats_host, int32_t* status_host, int64_t* totals);
+
 /* ---- DiffSL front end: what OdeBuilder::build_from_diffsl does with the external `diffsl` compiler
  * (crates/diffsol/src/ode_solver/builder.rs, crates/diffsol/src/ode_equations/diffsl.rs): DiffSL text -> source code of the model.
  * target DSHS_DIFFSL_HIP_STATIC: `struct dsh::JitModel` (n <= 8, register-resident; feeds dsh_model_compile);

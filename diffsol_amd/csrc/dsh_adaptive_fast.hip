@@ -13,6 +13,10 @@
 // Lock-step groups whose options are the defaults take k_bdf_adaptive<.., FAST, DEFOPT = true>: the options the kernel body reads are compile-time constants there
 // (DSH_ADAPTIVE_BODY_OPTIONS, dsh_adaptive_kernel.hpp: the one list behind dsh_adaptive_default_options(), the kernel's constant view and body_options_are_default
 // below), so that no option is loaded on the per-step chain.  Bit for bit the general fast kernel's results (profiles/default_options_kernel.md).  This is the instantiation bench.py times.
+// It also takes the first Newton iteration's convergence test by ballot: every lane compares its own weighted mean square with a threshold formed ahead of the solve
+// (ballot_decide_below, dsh_adaptive_kernel.hpp), so a step that converges in one iteration runs no wavefront reduction, and one that does not reduces that norm in
+// the second iteration's block, where its value is first read (behind that iteration's substitution, as the compiler schedules it).  The first two iterations are
+// peeled for that; eta^0.8 and the threshold are formed in the first solve's block.  Same values, same decisions: still the general fast kernel's bits (profiles/ballot_decisions.md, tests/test_gpu_ballot_decisions.py).
 //
 // Its results are NOT bit-comparable with the oracle (every other kernel of the library is); north_star asks for 1e-6 relative on the states,
 // which the tests hold it to at tight tolerances; at the bench's full size it makes the step decisions of the exact kernel (every member's five counters equal,

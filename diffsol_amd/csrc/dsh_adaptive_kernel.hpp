@@ -120,8 +120,8 @@ __device__ __forceinline__ double group_norm_w(double v) {
 // single-precision seed a relative error below 4e-6 over the whole domain): the seed exp2(-0.2 log2 x) by the hardware's f32 transcendentals, then three
 // division-free Newton steps w += 0.2 w (1 - x w^5) in FP64 for the inverse fifth root.  A relative error e becomes 3 e^2: 4e-6, 5e-11, 8e-21, so the
 // last step leaves w within about 1 ulp (the rounding of its own residual and update) and the product adds half an ulp.
-__device__ __forceinline__ double pow_p08(double x) {
-  if (__builtin_expect(!(x > 0x1p-100 && x < 0x1p100), 0)) return rpow(x, 0.8, false);
+__device__ __forceinline__ bool pow_p08_domain(double x) { return x > 0x1p-100 && x < 0x1p100; }
+__device__ __forceinline__ double pow_p08_inline(double x) {  // the arithmetic alone, for x inside pow_p08_domain
   double w = (double)__builtin_amdgcn_exp2f(-0.2f * __builtin_amdgcn_logf((float)x));
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
@@ -130,6 +130,48 @@ __device__ __forceinline__ double pow_p08(double x) {
     w = fma(0.2 * w, fma(-x, w5, 1.0), w);
   }
   return x * w;
+}
+__device__ __forceinline__ double pow_p08(double x) {
+  if (__builtin_expect(!pow_p08_domain(x), 0)) return rpow(x, 0.8, false);
+  return pow_p08_inline(x);
+}
+
+// FAST, lock-step groups with the default options (k_bdf_adaptive<.., FAST, WAVE, DEFOPT>): group decisions by ballot.  The rule: a decision of the form
+// "g(max over the lanes of v) < bound" is taken as "every lane's v is below a threshold" with one compare per lane and a scalar test of the ballot, and the wavefront
+// maximum is formed where its VALUE is read instead of ahead of the branch (six dependent DPP stages, a v_readlane and, for a norm, a sqrt: some 40 dependent
+// instructions of an in-order wavefront that nothing else fills at 1.5 wavefronts per SIMD), so the paths that never read it do not pay for it.  Every value keeps the instructions that compute
+// it today and every decision is provably today's, so the kernel stays bit-identical to the general fast kernel, which keeps the reductions in front of its branches.
+//
+// ballot_decide_below(v, T): v is each lane's non-negative value, T a wavefront-uniform threshold.  kBallotAllBelow: every lane has v < T (1 - 2^-40);
+// kBallotSomeAbove: every lane is on one side of the band and some lane has v >= T (1 + 2^-40); kBallotUndecided otherwise: a lane inside the band, a NaN lane (it
+// fails both compares), or a T that is not positive, finite and normal.  Two v_cmp_f64 and scalar tests of the two ballots.  All 64 lanes must be active (the contract
+// of group_norm_w).  The caller sends an undecided wavefront through the reduction-based test unchanged, as cold code behind one scalar branch.
+//
+// Why the band makes the two forms agree (first Newton iteration: today eta08 * sqrt(M) < tol with M = max v; here v < thr2 = (tol / eta08)^2 in every lane).  In exact
+// arithmetic the two are the same statement.  Today's left side carries the fast build's sqrt (v_rsq_f64 and two refinements: within 2 units of 2^-53) and one
+// rounding of the product: as a bound on M, twice that, about 5 units.  thr2 carries the reciprocal-math quotient (within 2 units), doubled by the square, and the
+// square's rounding: about 5 units; the two band edges one rounding each.  So the computed forms can disagree only for an M within about 12 units of 2^-53 of thr2, and
+// the band is 2^13 = 8192 units wide either side.  Outside it both say the same: M below the lower edge means every lane is (the maximum IS a lane's value, no
+// arithmetic touches it), M at or above the upper edge means that lane is.  Correctness does not rest on the band being hit rarely; speed does (a random M lands in
+// it with probability 2^-39 per decade of its distribution).  Underflow: near the threshold the product eta08 * sqrt(M) is near tol = 0.2, far from the denormals; far
+// from the threshold a denormal product is still below tol.  +inf in a lane is above every finite edge; zero and denormals are below every normal one.
+enum : int { kBallotAllBelow = 0, kBallotSomeAbove = 1, kBallotUndecided = 2 };
+__device__ __forceinline__ int ballot_decide_below(double v, double T) {
+  const bool t_ok = T >= 0x1p-1022 && T <= 0x1.fffffffffffffp1023;  // positive, normal, finite (false for a NaN)
+  const unsigned long long below = __builtin_amdgcn_ballot_w64(v < T * (1.0 - 0x1p-40));
+  const unsigned long long above = __builtin_amdgcn_ballot_w64(v >= T * (1.0 + 0x1p-40));
+  if (__builtin_expect(!t_ok || (below | above) != ~0ull, 0)) return kBallotUndecided;
+  return above != 0ull ? kBallotSomeAbove : kBallotAllBelow;
+}
+// The first Newton iteration's convergence test, Convergence::check_new_iteration with no previous norm: eta08 * sqrt(max dms) < tol.  thr2 comes from
+// newton_first_threshold(tol, eta08), formed ahead of the solve (eta is known before the iteration starts).  `undecided` reports the cold path (tests/ballot_decide_check).
+// eta08 is positive or a NaN (eta is clamped from below before its power is taken); a NaN, zero or infinite eta08 gives a threshold that fails t_ok.
+__device__ __forceinline__ double newton_first_threshold(double tol, double eta08) { const double q = tol / eta08; return q * q; }
+__device__ __forceinline__ bool newton_first_converged(double dms, double thr2, double eta08, double tol, bool& undecided) {
+  const int d = ballot_decide_below(dms, thr2);
+  undecided = d == kBallotUndecided;
+  if (__builtin_expect(undecided, 0)) return eta08 * sqrt(wave_max_nonneg_f64(dms)) < tol;
+  return d == kBallotAllBelow;
 }
 // x^(1/k) for x positive, normal and finite: sqrt for k = 2, cbrt for k = 3 (the convergence rate of the third and fourth Newton iteration; the ratio is
 // almost always in (0, 1)).  Every other k, and every other x, is the general call with the exponent as the call site wrote it.
@@ -212,6 +254,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DSH_ADAPTIVE
   // @phase set-up (init, consistent state, first factorisation)
   constexpr int N = Mdl::N, NP = Mdl::NP;
   constexpr int NR = Mdl::NROOTS > 0 ? Mdl::NROOTS : 1;
+  constexpr bool BALLOT = FAST && WAVE && DEFOPT;  // the first Newton iteration's convergence test by ballot, its reduction where the value is read (ballot_decide_below above)
+  static_assert(!BALLOT || (!SEG && !SENS), "decisions by ballot: lock-step groups of the plain fast kernel");
   const AdaptiveConsts& C = *Cp;
   const int ML = (!WAVE && !SEG && C.r.member_lanes > 0) ? C.r.member_lanes : 64;  // members per wavefront under per-member control (see ResidentConsts)
   const int64_t bglobal = (int64_t)blockIdx.x * ML + threadIdx.x;
@@ -688,6 +732,109 @@ DSH_UNROLL_N
       bool has_old = false;
       double old_norm = 0.0;
       bool solved = false;
+      if constexpr (BALLOT) {
+        // The loop of the else arm with its first two iterations peeled and the first convergence test taken by ballot (ballot_decide_below above): the same
+        // arithmetic on the same values, the same decisions.  What moves is where the wavefront maxima are formed.
+        const double tol = o.nonlinear_solver_tolerance;
+        // one Newton update: residual, solve, x -= delta; dms = the lane's weighted mean square of the update.  false: LuSolveFailed, nothing updated.
+        // `beside` is work that does not depend on the solve and is to share its basic block.  It is called behind the lu_ok test because that is where the
+        // compiler puts the residual and the substitution: lu_ok depends on the factors alone, so the test comes out AHEAD of them as a scalar branch.
+        // This body is the else arm's loop body a second time (residual, solve, x -= d, weighted mean square): a change to either must be made in the other, and
+        // tests/test_gpu_ballot_decisions.py holds the two to the same bits on the models it runs.
+        auto newton_update = [&](double& dms, auto&& beside) __attribute__((always_inline)) -> bool {
+          double f[N], delta[N], tmpv[N];
+          Mdl::rhs(t_predict, x, p, f);
+          if constexpr (Mdl::HAS_MASS) {
+DSH_UNROLL_N
+            for (int i = 0; i < N; ++i) { tmpv[i] = x[i] + psi[i]; delta[i] = f[i]; }
+            Mdl::mass_gemv(t_predict, tmpv, p, -opc, delta);
+          } else {
+DSH_UNROLL_N
+            for (int i = 0; i < N; ++i) delta[i] = 1.0 * (x[i] + psi[i]) + (-opc) * f[i];
+          }
+          bool solved_ok;
+          if constexpr (BANDED) solved_ok = band_solve_lane<N, BK>(Lf, Uf, P, delta);
+          else solved_ok = lu_solve_reg_inv<N>(A, Adinv, P, delta);
+          if (!group_all<WAVE>(solved_ok)) return false;
+          // The else arm's x - d subtracts the ROUNDED d: there the substitution's last multiply (by the reciprocal of the pivot) and this subtraction end up in different
+          // basic blocks and are not contracted.  Here they share one, and -ffp-contract=fast would make x - t / pivot one fma with one rounding: the states would
+          // differ from the general kernel's in the last bits.  Behind the empty asm d is a value like any other.
+DSH_UNROLL_N
+          for (int i = 0; i < N; ++i) asm volatile("" : "+v"(delta[i]));
+          beside();
+          double acc = 0.0;
+DSH_UNROLL_N
+          for (int i = 0; i < N; ++i) {
+            const double d = delta[i];
+            x[i] = x[i] - d;
+            const double term = d * winv[i];
+            acc += term * term;
+          }
+          dms = acc / (double)N;
+          return true;
+        };
+        // the rate test of an iteration >= 2 (niter already counts it): 0 go on, 1 converged, 2 diverged; eta as the else arm leaves it
+        auto rate_test = [&](double norm, double old_nrm) __attribute__((always_inline)) -> int {
+          const double rate = niter == 2 ? norm / old_nrm : uniform<WAVE>(root_k(norm / old_nrm, niter - 1));
+          if (rate > 0.9) return 2;
+          if (powi_rate<FAST>(rate, o.max_nonlinear_solver_iterations - niter) / (1.0 - rate) * norm > tol) return 2;
+          eta = rate / (1.0 - rate);
+          return eta * norm < tol ? 1 : 0;
+        };
+        // ---- iteration 1.  eta^0.8 and the threshold of the ballot are formed AHEAD of the solve, in its basic block: they do not depend on it.  The same
+        // constants-or-pow_p08 selection as the else arm, as selects; an eta outside pow_p08's domain makes the call after the solve (cold).  eta itself is written
+        // where the else arm writes it: after lu_ok.
+        const double min_eta = 1e4 * 2.220446049250313e-16;
+        const double eta_c = eta < min_eta ? min_eta : eta;
+        const double reset_a = C.r.eta_reset, reset_b = C.r.eta_reset_ts, p08_a = C.eta_reset_p08, p08_b = C.eta_reset_ts_p08;
+        const bool is_a = eta_c == reset_a, is_b = eta_c == reset_b, in_dom = pow_p08_domain(eta_c);
+        const bool needs_call = !(is_a | is_b | in_dom);
+        double eta08 = 0.0, thr2 = 0.0;
+        double dms1;
+        if (newton_update(dms1, [&]() __attribute__((always_inline)) {
+              // formed whether or not a reset constant is taken below, inside the solve's block; the empty asm keeps the compiler from sinking it behind the
+              // selects' conditions.  As compiled, its seed starts among the substitution's last instructions and its three Newton steps follow the substitution;
+              // the quotient tol / eta08 runs between the instructions of the update and the weighted sum (profiles/ballot_decisions.md, section 2).
+              double pw = pow_p08_inline(in_dom ? eta_c : 1.0);
+              asm volatile("" : "+v"(pw));
+              eta08 = is_a ? p08_a : (is_b ? p08_b : uniform<WAVE>(pw));
+              thr2 = newton_first_threshold(tol, eta08);
+            })) {
+          if (__builtin_expect(needs_call, 0)) { eta08 = uniform<WAVE>(rpow(eta_c, 0.8, false)); thr2 = newton_first_threshold(tol, eta08); }
+          eta = eta08;
+          niter = 1;
+          bool undecided;
+          if (newton_first_converged(dms1, thr2, eta08, tol, undecided)) solved = true;
+          else if (o.max_nonlinear_solver_iterations > 1) {
+            // ---- iteration 2.  The first update's norm, which nothing has read so far, is reduced HERE, in the basic block of this iteration's residual and
+            // substitution, of which it is independent.  As compiled the six stages follow the substitution, two instructions of the update and the weighted sum
+            // between each, and the read of lane 63 and the sqrt end the block alone: the reduction has left the first iteration's path, it is not hidden under this
+            // solve (profiles/ballot_decisions.md, section 2).  A wavefront with a NaN lane takes the two-pass reduction first, as
+            // wave_max_nonneg_f64 does; the chain then runs for nothing and its result is dropped.
+            double nan_nrm = 0.0;
+            const bool nan1 = wave_any_nan(dms1);
+            if (__builtin_expect(nan1, 0)) nan_nrm = sqrt(wave_max_nonneg_f64(dms1));
+            double nrm1 = 0.0;
+            double dms2;
+            if (newton_update(dms2, [&]() __attribute__((always_inline)) { nrm1 = sqrt(wave_max_nonneg_f64_chain(dms1)); })) {
+              const double old_nrm = nan1 ? nan_nrm : nrm1;
+              double norm = sqrt(group_norm_w<WAVE>(dms2));
+              niter = 2;
+              int r = rate_test(norm, old_nrm);
+              if (r == 1) solved = true;
+              // ---- iterations >= 3: the else arm's loop body
+              for (int it = 2; r == 0 && it < o.max_nonlinear_solver_iterations; ++it) {
+                double dms;
+                if (!newton_update(dms, []() {})) break;
+                norm = sqrt(group_norm_w<WAVE>(dms));
+                niter += 1;
+                r = rate_test(norm, old_nrm);
+                if (r == 1) solved = true;
+              }
+            }
+          }
+        }
+      } else
       for (int it = 0; it < o.max_nonlinear_solver_iterations; ++it) {
         double f[N], delta[N], tmpv[N];
         Mdl::rhs(t_predict, x, p, f);

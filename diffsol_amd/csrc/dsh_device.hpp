@@ -108,8 +108,12 @@ template <int CTRL>
 __device__ __forceinline__ double dpp_max_f64(double v) {
   return __builtin_fmax(v, __hiloint2double(__builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, true), __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, true)));
 }
-__device__ __forceinline__ double wave_max_nonneg_f64(double v) {
-  if (__builtin_expect(__builtin_amdgcn_ballot_w64(v != v) != 0ull, 0)) return __longlong_as_double((long long)wave_max_u64(d2u(v)));
+// The two halves of wave_max_nonneg_f64 (below) apart, for a caller that wants the six stages in a basic block of its own choosing and the NaN test
+// elsewhere: wave_any_nan is the ballot, wave_max_nonneg_f64_chain the stages and the read of lane 63 with NO NaN test.
+// The chain's result is wave_max_nonneg_f64's bit for bit when no lane holds a NaN and is meaningless otherwise: the caller tests wave_any_nan and takes
+// wave_max_nonneg_f64 for such a wavefront.  All 64 lanes must be active, the argument must not be negative.
+__device__ __forceinline__ bool wave_any_nan(double v) { return __builtin_amdgcn_ballot_w64(v != v) != 0ull; }
+__device__ __forceinline__ double wave_max_nonneg_f64_chain(double v) {
   v = dpp_max_f64<kDppQuadXor1>(v);
   v = dpp_max_f64<kDppQuadXor2>(v);
   v = dpp_max_f64<kDppRowHalfMirror>(v);
@@ -117,6 +121,10 @@ __device__ __forceinline__ double wave_max_nonneg_f64(double v) {
   v = dpp_max_f64<kDppRowBcast15>(v);
   v = dpp_max_f64<kDppRowBcast31>(v);
   return __longlong_as_double((long long)readlane_u64(d2u(v), 63));
+}
+__device__ __forceinline__ double wave_max_nonneg_f64(double v) {
+  if (__builtin_expect(wave_any_nan(v), 0)) return __longlong_as_double((long long)wave_max_u64(d2u(v)));
+  return wave_max_nonneg_f64_chain(v);
 }
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
   v += dpp_move_u64<kDppQuadXor1>(v);

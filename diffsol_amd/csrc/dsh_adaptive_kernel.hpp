@@ -254,8 +254,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DSH_ADAPTIVE
   // @phase set-up (init, consistent state, first factorisation)
   constexpr int N = Mdl::N, NP = Mdl::NP;
   constexpr int NR = Mdl::NROOTS > 0 ? Mdl::NROOTS : 1;
-  constexpr bool BALLOT = FAST && WAVE && DEFOPT;  // the first Newton iteration's convergence test by ballot, its reduction where the value is read (ballot_decide_below above)
-  static_assert(!BALLOT || (!SEG && !SENS), "decisions by ballot: lock-step groups of the plain fast kernel");
+  // The lock-step fast kernel with the default options, the instantiation bench.py times: the first Newton iteration's convergence test by ballot with its reduction
+  // where the value is read (ballot_decide_below above), and the error-test failure's controller exponent formed in that block instead of at the head of every step.
+  constexpr bool LOCKFAST = FAST && WAVE && DEFOPT;
+  static_assert(!LOCKFAST || (!SEG && !SENS), "decisions by ballot: lock-step groups of the plain fast kernel");
   const AdaptiveConsts& C = *Cp;
   const int ML = (!WAVE && !SEG && C.r.member_lanes > 0) ? C.r.member_lanes : 64;  // members per wavefront under per-member control (see ResidentConsts)
   const int64_t bglobal = (int64_t)blockIdx.x * ML + threadIdx.x;
@@ -732,7 +734,7 @@ DSH_UNROLL_N
       bool has_old = false;
       double old_norm = 0.0;
       bool solved = false;
-      if constexpr (BALLOT) {
+      if constexpr (LOCKFAST) {
         // The loop of the else arm with its first two iterations peeled and the first convergence test taken by ballot (ballot_decide_below above): the same
         // arithmetic on the same values, the same decisions.  What moves is where the wavefront maxima are formed.
         const double tol = o.nonlinear_solver_tolerance;
@@ -1079,7 +1081,13 @@ DSH_UNROLL_N
         break;
       }
       // @phase error-test failure
-      double factor = safety * uniform<WAVE>(pi_controller_raw(error_norm, has_prev_err, prev_err, o.pi_control_integral, o.pi_control_proportional, order + 1, det));
+      // LOCKFAST: the controller's exponent -(pi_control_integral / (order + 1)) is read here only.  With the options compiled in nothing of it depends on the retry
+      // loop, and it was hoisted to the head of EVERY step: a conversion, a reciprocal with two refinements, the product and its correction, ten dependent instructions
+      // and a register pair for a value an accepted step never reads (profiles/step_chain_round_trips.md).  Behind the empty asm the order is a value the compiler
+      // cannot see through, so the exponent is formed here.  The same operations on the same operands: the bits do not change.
+      int eff_order = order + 1;
+      if constexpr (LOCKFAST) { eff_order = uniform<WAVE>(eff_order); asm volatile("" : "+s"(eff_order)); }
+      double factor = safety * uniform<WAVE>(pi_controller_raw(error_norm, has_prev_err, prev_err, o.pi_control_integral, o.pi_control_proportional, eff_order, det));
       has_prev_err = false;
       if (factor < o.min_timestep_shrink) factor = o.min_timestep_shrink;
       double new_h;

@@ -215,15 +215,9 @@ int bdf_solve_adaptive_impl(dsh_ctx* ctx, int model, int64_t size, int64_t nb, c
     for (int64_t i = 0; i < 4 && i < ns; ++i) C.sens_atol[i] = sens->natol == 0 ? 0.0 : (sens->natol == 1 ? sens->atol_host[0] : sens->atol_host[i]);
   }
   {  // Bdf::_new tables (bdf.rs:286-306)
-    const double kappa[6] = {0.0, -0.1850, -1.0 / 9.0, -0.0823, -0.0415, 0.0};
-    C.alpha[0] = 0.0; C.gamma[0] = 0.0; C.ec2[0] = 1.0;
-    for (int i = 1; i <= kMaxOrder; ++i) {
-      const double i_t = (double)i, one_over_i = 1.0 / i_t, one_over_i_plus_one = 1.0 / (i_t + 1.0);
-      C.gamma[i] = C.gamma[i - 1] + one_over_i;
-      C.alpha[i] = 1.0 / ((1.0 - kappa[i]) * C.gamma[i]);
-      const double e = kappa[i] * C.gamma[i] + one_over_i_plus_one;
-      C.ec2[i] = e * e;
-    }
+    // the one function the per-order bodies of the lock-step fast kernel evaluate at compile time (dsh_bdf_tables.hpp): the same 64-bit patterns
+    const BdfTables T = bdf_new_tables();
+    for (int i = 0; i <= kMaxOrder; ++i) { C.alpha[i] = T.alpha[i]; C.gamma[i] = T.gamma[i]; C.ec2[i] = T.ec2[i]; }
     C.r.eta_reset = std::pow(20.0, 1.25);
     C.r.eta_reset_ts = std::pow(100.0, 1.25);
     C.eta_reset_p08 = dsh_det_pow(C.r.eta_reset, 0.8);  // used by the kernel only with the deterministic pow (the same function there)

@@ -17,6 +17,9 @@
 // (ballot_decide_below, dsh_adaptive_kernel.hpp), so a step that converges in one iteration runs no wavefront reduction, and one that does not reduces that norm in
 // the second iteration's block, where its value is first read (behind that iteration's substitution, as the compiler schedules it).  The first two iterations are
 // peeled for that; eta^0.8 and the threshold are formed in the first solve's block.  Same values, same decisions: still the general fast kernel's bits (profiles/ballot_decisions.md, tests/test_gpu_ballot_decisions.py).
+// Its prediction, its update of the differences and the norms of its order selection have a body per order behind one scalar dispatch on the wavefront-uniform order
+// (with_order, dsh_adaptive_kernel.hpp) with that order's Bdf::_new coefficients as constants (dsh_bdf_tables.hpp): the same operations per component, the same bits
+// (profiles/order_paths.md, tests/test_gpu_order_paths.py).
 //
 // Its results are NOT bit-comparable with the oracle (every other kernel of the library is); north_star asks for 1e-6 relative on the states,
 // which the tests hold it to at tight tolerances; at the bench's full size it makes the step decisions of the exact kernel (every member's five counters equal,

@@ -2,6 +2,7 @@
 // modules (dsh_jit.hip) instantiate the same kernel for user models.
 #pragma once
 #include "dsh_resident.hpp"
+#include "dsh_bdf_tables.hpp"
 
 namespace dsh {
 
@@ -79,6 +80,37 @@ __device__ __forceinline__ void guarded(bool c, F&& f) {
     f();
   }
 }
+
+// FAST, lock-step groups with the default options (LOCKFAST in k_bdf_adaptive): per-order step bodies.  The guarded loops above ask the order per column — a scalar
+// compare and a branch each, 29 on an accepted step, with the copies that carry values across their joins.  with_order() is ONE scalar dispatch on the
+// wavefront-uniform order (at most three compare-and-branch) into a body compiled for that order: constant trip counts, D[Q + 1] a named register, no guard and no
+// select on the order.  Per component a body runs the guarded form's operations on its operands in its order, so the bits are the general fast kernel's
+// (tests/test_gpu_order_paths.py).  The order is 1..kMaxOrder by construction; any other value would take the last body.
+template <int Q> struct order_c { static constexpr int value = Q; };
+template <class F>
+__device__ __forceinline__ void with_order(int ou, F&& f) {
+  if (ou <= 2) {
+    if (ou <= 1) f(order_c<1>{}); else f(order_c<2>{});
+  } else {
+    if (ou == 3) f(order_c<3>{});
+    else if (ou == 4) f(order_c<4>{});
+    else f(order_c<5>{});
+  }
+}
+// The three parts that have per-order bodies, each with its switch (profiles/order_paths.md has every part measured alone), and the Bdf::_new coefficients of a
+// body's order as compile-time constants (kBdfTables, dsh_bdf_tables.hpp: the bits of the tables the host fills, tests/test_bdf_tables.py) instead of LDS reads.
+#ifndef DSH_ORDER_PATHS_PREDICT
+#define DSH_ORDER_PATHS_PREDICT 1
+#endif
+#ifndef DSH_ORDER_PATHS_UPDATE
+#define DSH_ORDER_PATHS_UPDATE 1
+#endif
+#ifndef DSH_ORDER_PATHS_SELECT
+#define DSH_ORDER_PATHS_SELECT 1
+#endif
+#ifndef DSH_ORDER_PATHS_LITERALS
+#define DSH_ORDER_PATHS_LITERALS 1
+#endif
 
 // A value that is the same in all 64 lanes of a wavefront lock-step group, moved to scalar registers (v_readfirstlane on every 32-bit half).  The
 // compiler cannot see that such a value is uniform when it comes back from a function call (rpow is not inlined) or is carried round the step loop
@@ -258,6 +290,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DSH_ADAPTIVE
   // where the value is read (ballot_decide_below above), and the error-test failure's controller exponent formed in that block instead of at the head of every step.
   constexpr bool LOCKFAST = FAST && WAVE && DEFOPT;
   static_assert(!LOCKFAST || (!SEG && !SENS), "decisions by ballot: lock-step groups of the plain fast kernel");
+  constexpr bool kLit = DSH_ORDER_PATHS_LITERALS != 0;  // per-order bodies (with_order above): the order's coefficients as constants
   const AdaptiveConsts& C = *Cp;
   const int ML = (!WAVE && !SEG && C.r.member_lanes > 0) ? C.r.member_lanes : 64;  // members per wavefront under per-member control (see ResidentConsts)
   const int64_t bglobal = (int64_t)blockIdx.x * ML + threadIdx.x;
@@ -572,7 +605,39 @@ DSH_UNROLL_N
   // @phase predict_forward
   // _predict_forward (bdf.rs:674-692): y_predict = sum_{j<=order} D_j ; psi_neg_y0 = alpha_order * sum_{1<=j<=order} gamma_j D_j - y_predict
   auto predict_forward = [&]() __attribute__((always_inline)) {
-    if constexpr (WAVE) {
+    if constexpr (LOCKFAST && DSH_ORDER_PATHS_PREDICT != 0) {
+      // the WAVE arm below in a body per order (with_order above): s and q column by column as there, q from gamma_1 D_1, then q alpha_Q - s
+      with_order(uniform<WAVE>(order), [&](auto qc) __attribute__((always_inline)) {
+        constexpr int Q = decltype(qc)::value;
+        constexpr BdfTables T = bdf_new_tables();
+        double g1;
+        if constexpr (kLit) { g1 = T.gamma[1]; asm volatile("" : "+s"(g1)); }  // gamma_1 is 1.0: behind the empty asm the product stays the multiplication it is in the general kernel
+        else g1 = sGamma[1];
+        double s[N], q[N];
+DSH_UNROLL_N
+        for (int i = 0; i < N; ++i) { s[i] = 0.0; q[i] = g1 * D[1][i]; }
+#pragma unroll
+        for (int j = 0; j <= Q; ++j) {
+DSH_UNROLL_N
+          for (int i = 0; i < N; ++i) s[i] = s[i] + D[j][i];
+          if (j >= 2) {
+            // fma() spelled out, here and in the tail: this translation unit is compiled with -ffp-contract=fast, and in the general kernel gamma_j D_j + q and
+            // q alpha - s each sit in one basic block and are ALWAYS one fused multiply-add.  Which pairs fuse depends on what shares a block: with the guards gone the
+            // compiler fused gamma_1 D_1 into the sum instead of gamma_2 D_2, and hoisted products that all bodies share above the dispatch, where they no longer fuse
+            // (both seen in the assembly, both moved the states' last bits).  The intrinsic is the general kernel's instruction whatever the blocks are.
+            const double gj = kLit ? T.gamma[j] : sGamma[j];
+DSH_UNROLL_N
+            for (int i = 0; i < N; ++i) q[i] = fma(gj, D[j][i], q[i]);
+          }
+        }
+        const double al = kLit ? T.alpha[Q] : sAlpha[Q];
+DSH_UNROLL_N
+        for (int i = 0; i < N; ++i) {
+          yp[i] = s[i];
+          psi[i] = fma(q[i], al, -s[i]);
+        }
+      });
+    } else if constexpr (WAVE) {
       const int ou = __builtin_amdgcn_readfirstlane(order);
       double s[N], q[N];
 DSH_UNROLL_N
@@ -1013,7 +1078,26 @@ DSH_UNROLL_N
       if (error_norm <= 1.0) {
         // @phase accept: update of the differences
         // ---- accepted: _update_diff (bdf.rs:646-664), state update
-        if constexpr (WAVE) {
+        if constexpr (LOCKFAST && DSH_ORDER_PATHS_UPDATE != 0) {
+          // the WAVE arm below in a body per order: D_{Q+2} = ydelta - D_{Q+1}, D_{Q+1} = ydelta, the cascade from j = Q down to 0
+          with_order(uniform<WAVE>(order), [&](auto qc) __attribute__((always_inline)) {
+            constexpr int Q = decltype(qc)::value;
+            double upper[N];
+DSH_UNROLL_N
+            for (int i = 0; i < N; ++i) {
+              const double dk1 = D[Q + 1][i];
+              D[Q + 2][i] = ydelta[i] - dk1;
+              D[Q + 1][i] = ydelta[i];
+              upper[i] = ydelta[i];
+            }
+#pragma unroll
+            for (int j = Q; j >= 0; --j)
+DSH_UNROLL_N
+              for (int i = 0; i < N; ++i) { const double v = D[j][i] + 1.0 * upper[i]; D[j][i] = v; upper[i] = v; }
+          });
+DSH_UNROLL_N
+          for (int i = 0; i < N; ++i) y[i] = yp[i];
+        } else if constexpr (WAVE) {
           const int ou = __builtin_amdgcn_readfirstlane(order);
           double dk1[N], upper[N];
 DSH_UNROLL_N
@@ -1106,6 +1190,19 @@ DSH_UNROLL_N
     if (n_equal_steps > order) {
       // order selection (bdf.rs:1494-1560): predict_error_control(order-1) / (order+1) on the updated differences
       double col_m[N], col_p[N];
+      const double inf = __builtin_huge_val();
+      double error_m_norm, error_p_norm;
+      if constexpr (LOCKFAST && DSH_ORDER_PATHS_SELECT != 0) {
+        // a body per order: the two norms straight from the columns D_Q and D_{Q+2} (no pick, no copy), the neighbour that does not exist at order 1 / kMaxOrder
+        // decided at compile time
+        with_order(uniform<WAVE>(order), [&](auto qc) __attribute__((always_inline)) {
+          constexpr int Q = decltype(qc)::value;
+          constexpr BdfTables T = bdf_new_tables();
+          error_m_norm = inf; error_p_norm = inf;
+          if constexpr (Q > 1) error_m_norm = group_norm_w<WAVE>(wms_y(D[Q])) * (kLit ? T.ec2[Q - 1] : sEc2[Q - 1]);
+          if constexpr (Q < kMaxOrder) error_p_norm = group_norm_w<WAVE>(wms_y(D[Q + 2])) * (kLit ? T.ec2[Q < kMaxOrder ? Q + 1 : Q] : sEc2[Q < kMaxOrder ? Q + 1 : Q]);
+        });
+      } else {
       if constexpr (WAVE) {
         const int ou = __builtin_amdgcn_readfirstlane(order);
 DSH_UNROLL_N
@@ -1130,9 +1227,9 @@ DSH_UNROLL_N
         col_m[i] = vm; col_p[i] = vp;
       }
       }
-      const double inf = __builtin_huge_val();
-      double error_m_norm = order > 1 ? group_norm_w<WAVE>(wms_y(col_m)) * sEc2[order - 1] : inf;
-      double error_p_norm = order < kMaxOrder ? group_norm_w<WAVE>(wms_y(col_p)) * sEc2[order + 1] : inf;
+      error_m_norm = order > 1 ? group_norm_w<WAVE>(wms_y(col_m)) * sEc2[order - 1] : inf;
+      error_p_norm = order < kMaxOrder ? group_norm_w<WAVE>(wms_y(col_p)) * sEc2[order + 1] : inf;
+      }
       if constexpr (SENS) {  // predict_error_control with the augmented system (bdf.rs:871-932): the `error_norm.max(err)` chain from zero, then the sensitivities' terms
         if (order > 1) error_m_norm = fmax(0.0, error_m_norm);
         if (order < kMaxOrder) error_p_norm = fmax(0.0, error_p_norm);

@@ -42,18 +42,64 @@ struct ErkConsts {
   // steps_t_out [steps_cap][nb]; columns beyond steps_cap are counted, not stored) instead of interpolating at save points
   double* steps_t_out;
   int steps_cap, steps_pad;
+  // Forward sensitivities (k_erk_resident<.., SENS = true>; problem.tsit45_sens(), explicit_rk.rs:46-54): s_j = dy/dp_j of every parameter integrated alongside.
+  // The fields have the meaning of AdaptiveConsts' (dsh_adaptive_kernel.hpp): sens_out n_eval x NP x N x nb (device, batch-fastest); sens_error_control != 0: the
+  // sensitivities take part in the error test with sens_rtol / sens_atol (SensEquations::include_in_error_control), else they do not; sens_pad = 1: sens_atol[0] for
+  // every state.  Appended: a kernel without sensitivities never reads them.
+  double* sens_out;
+  double sens_rtol, sens_atol[4];
+  int sens_error_control, sens_pad;
 };
+
+// Doubles a lane keeps: 14 N without sensitivities (7 stage increments, y, dy, old_y, stage point, stage derivative, error vector, atol), 12 N more per parameter
+// with them (7 stage increments, s, ds, old_s, stage point, stage derivative).  The plain kernel's largest instantiation (N = 8: 112 doubles) compiles without
+// scratch memory; a model with forward sensitivities is admitted up to the same count.
+constexpr int kErkMaxLaneDoubles = 112;
+__host__ __device__ constexpr bool erk_sens_admitted(int64_t n, int64_t np) { return n >= 1 && np >= 1 && n * (14 + 12 * np) <= kErkMaxLaneDoubles; }
+
+// The two halves of interpolate_inplace (runge_kutta.rs:968-981 interpolate_beta_function, :962-966 interpolate_from_diff) apart, for the kernel with sensitivities:
+// the beta function of a save point is computed once and applied to the state and to every sensitivity (interpolate_sens_inplace, :1237-1309).  The operations and
+// their order are those of the kernel's `interpolate`.
+__device__ __forceinline__ void erk_beta_function(double t, double old_t, double tt, double (&bf)[kErkStages]) {
+  const double dt = t - old_t;
+  const double theta = dt == 0.0 ? 1.0 : (tt - old_t) / dt;
+  double thetav[kErkPoly];
+  thetav[0] = theta;
+#pragma unroll
+  for (int q = 1; q < kErkPoly; ++q) thetav[q] = theta * thetav[q - 1];
+#pragma unroll
+  for (int i = 0; i < kErkStages; ++i) {
+    double acc = 1.0 * kTsitBeta[0][i] * thetav[0];
+#pragma unroll
+    for (int q = 1; q < kErkPoly; ++q) acc = 1.0 * kTsitBeta[q][i] * thetav[q] + acc;
+    bf[i] = acc;
+  }
+}
+template <int N>
+__device__ __forceinline__ void erk_from_diff(const double (&bf)[kErkStages], const double (&y0)[N], const double (&df)[kErkStages][N], double (&ret)[N]) {
+DSH_UNROLL_N
+  for (int i = 0; i < N; ++i) {
+    double acc = 1.0 * df[0][i] * bf[0] + 1.0 * y0[i];
+#pragma unroll
+    for (int j = 1; j < kErkStages; ++j) acc = 1.0 * df[j][i] * bf[j] + acc;
+    ret[i] = acc;
+  }
+}
 
 // One lane per member: ExplicitRk::step (explicit_rk.rs:196-243) over the Rk core (runge_kutta.rs), root finding on the dense output, tstop, solve_dense /
 // solve.  Per lane: the 7 stage increments (diff, 7 x N), state and old state (y, dy, old_y), the error vector and the controller's scalars — no LDS.
 // The register allocator picks the occupancy (no waves-per-SIMD attribute): see DESIGN.md for the compiler's numbers.
-template <class Mdl, bool BA, bool WAVE>
+// SENS: ExplicitRk<.., SensEquations> — per parameter j the stage increments sdiff_j, s_j, ds_j, old_s_j and the stage point and its derivative, all in registers
+// (every loop over the parameters is unrolled: no array is indexed at run time); models within erk_sens_admitted() only.
+template <class Mdl, bool BA, bool WAVE, bool SENS = false>
 __global__ __launch_bounds__(64) void k_erk_resident(int64_t nb, const double* __restrict__ p_g, const double* __restrict__ atol_g, const ErkConsts* __restrict__ Cp,
                                                      const double* __restrict__ t_eval, double* __restrict__ y_out, int32_t* __restrict__ stats_out,
                                                      int32_t* __restrict__ status_out, double* __restrict__ t_root_out, int32_t* __restrict__ root_idx_out,
                                                      int32_t* __restrict__ ncols_out, unsigned long long* __restrict__ totals) {
   constexpr int N = Mdl::N, NP = Mdl::NP, NR = Mdl::NROOTS > 0 ? Mdl::NROOTS : 1, S = kErkStages;
   static_assert(!Mdl::HAS_MASS, "explicit Runge-Kutta methods take no mass matrix (MassMatrixNotSupported, runge_kutta.rs:236-239)");
+  static_assert(!SENS || Mdl::NROOTS == 0, "device-resident Tsit45 with forward sensitivities: models without root functions");
+  static_assert(!SENS || erk_sens_admitted(Mdl::N, Mdl::NP), "device-resident Tsit45 with forward sensitivities: N (14 + 12 NP) <= 112 doubles per lane");
   const ErkConsts& T = *Cp;
   const ResidentConsts& C = T.r;
   const dsh_adaptive_options& o = C.o;
@@ -90,6 +136,34 @@ DSH_UNROLL_N
   bool has_prev_err = false;
   double prev_err = 0.0;
   int n_steps = 0, n_err_fails = 0;
+
+  // ------------------------------------------------------------ RkState::new_with_sensitivities (state.rs:1001-1029), Rk::new_augmented
+  // s_j = SensInit(t0) e_j, ds_j = SensRhs(s_j) about (y0, t0) = J(y0) s_j + (df/dp) e_j (sens_equations.rs:168-174: the Jacobian product first); the step size
+  // above is the state equations' alone
+  constexpr int NPS = SENS ? NP : 1, NS = SENS ? N : 1, SS = SENS ? S : 1;
+  double sdiff[NPS][SS][NS], s[NPS][NS], ds[NPS][NS], old_s[NPS][NS], s_atol[NS];
+  // old_state.s / old_state.ds: the stage point of every sensitivity and its derivative.  Declared here and not next to sy / sdy in the step loop: an array in that
+  // scope, even unused, changes the schedule of the SENS = false kernel, which is to stay the kernel it was (profiles/erk_tsit45_sens.md)
+  double ss[NPS][NS], sds[NPS][NS];
+  if constexpr (SENS) {
+DSH_UNROLL_N
+    for (int i = 0; i < N; ++i) s_atol[i] = T.sens_atol[T.sens_pad != 0 ? 0 : (i < 4 ? i : 0)];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      double ev[NP], jm[N], dfdp[N];
+#pragma unroll
+      for (int k = 0; k < NP; ++k) ev[k] = k == j ? 1.0 : 0.0;
+      Mdl::init_sens_mul(t, p, ev, s[j]);
+      Mdl::sens_mul(t, y, p, ev, dfdp);
+      Mdl::jac_mul(t, y, p, s[j], jm);
+#pragma unroll
+      for (int q = 0; q < S; ++q)
+DSH_UNROLL_N
+        for (int i = 0; i < N; ++i) sdiff[j][q][i] = 0.0;
+DSH_UNROLL_N
+      for (int i = 0; i < N; ++i) { ds[j][i] = jm[i] + dfdp[i]; old_s[j][i] = s[j][i]; }
+    }
+  }
 
   // handle_tstop (runge_kutta.rs:752-781): 0 nothing, 1 reached, 2 StopTimeBeforeCurrentTime
   bool has_tstop = true;
@@ -132,7 +206,7 @@ DSH_UNROLL_N
   int col = 0;
   double t_root = 0.0;
   int root_idx = -1;
-  const bool steps_mode = T.steps_cap > 0;  // every accepted step out (ErkConsts::steps_cap)
+  const bool steps_mode = !SENS && T.steps_cap > 0;  // every accepted step out (ErkConsts::steps_cap)
   auto steps_write = [&](double tw, const double (&yw)[N]) __attribute__((always_inline)) {
     if (col < T.steps_cap && active) {
       T.steps_t_out[(int64_t)col * nb + b] = tw;
@@ -161,6 +235,12 @@ DSH_UNROLL_N
       // start_step_attempt (runge_kutta.rs:505-516): first same as last
 DSH_UNROLL_N
       for (int r = 0; r < N; ++r) diff[0][r] = hh * dy[r];
+      if constexpr (SENS) {  // :518-522
+#pragma unroll
+        for (int j = 0; j < NP; ++j)
+DSH_UNROLL_N
+          for (int r = 0; r < N; ++r) sdiff[j][0][r] = hh * ds[j][r];
+      }
 #pragma unroll
       for (int i = 1; i < S; ++i) {
         // do_stage (runge_kutta.rs:537-566): old_state.y = y + diff[:, 0..i] a_row_i (nalgebra gemv order), diff[:, i] = h f(old_state.y, t + c_i h)
@@ -175,6 +255,25 @@ DSH_UNROLL_N
         Mdl::rhs(ts, sy, p, sdy);
 DSH_UNROLL_N
         for (int r = 0; r < N; ++r) diff[i][r] = hh * sdy[r];
+        if constexpr (SENS) {  // :578-607: SensRhs about the stage point (sy, ts); old_state.s_j = s_j + sdiff_j[:, 0..i] a_row_i, sdiff_j[:, i] = h SensRhs(old_state.s_j)
+#pragma unroll
+          for (int j = 0; j < NP; ++j) {
+            double ev[NP], jm[N], dfdp[N];
+#pragma unroll
+            for (int k = 0; k < NP; ++k) ev[k] = k == j ? 1.0 : 0.0;
+DSH_UNROLL_N
+            for (int r = 0; r < N; ++r) {
+              double acc = 1.0 * sdiff[j][0][r] * erk_a(i, 0) + 1.0 * s[j][r];
+#pragma unroll
+              for (int q = 1; q < i; ++q) acc = 1.0 * sdiff[j][q][r] * erk_a(i, q) + acc;
+              ss[j][r] = acc;
+            }
+            Mdl::sens_mul(ts, sy, p, ev, dfdp);
+            Mdl::jac_mul(ts, sy, p, ss[j], jm);
+DSH_UNROLL_N
+            for (int r = 0; r < N; ++r) { sds[j][r] = jm[r] + dfdp[r]; sdiff[j][i][r] = hh * sds[j][r]; }
+          }
+        }
       }
       // error_norm (runge_kutta.rs:783-800): diff d, no linear solve
       double err[N];
@@ -186,6 +285,22 @@ DSH_UNROLL_N
         err[r] = acc;
       }
       error_norm = fmax(0.0, group_norm<WAVE>(wms<N>(err, y, atol, rtol)));
+      if constexpr (SENS) {  // :812-822: scaled by state.s_j at the start of the step; the states' norm, then j = 0, 1, ..
+        if (T.sens_error_control) {
+#pragma unroll
+          for (int j = 0; j < NP; ++j) {
+            double serr[N];
+DSH_UNROLL_N
+            for (int r = 0; r < N; ++r) {
+              double acc = 1.0 * sdiff[j][0][r] * kTsitD[0];
+#pragma unroll
+              for (int q = 1; q < S; ++q) acc = 1.0 * sdiff[j][q][r] * kTsitD[q] + acc;
+              serr[r] = acc;
+            }
+            error_norm = fmax(error_norm, group_norm<WAVE>(wms<N>(serr, s[j], s_atol, T.sens_rtol)));
+          }
+        }
+      }
       {  // Rk::factor (runge_kutta.rs:466-495) with safety_factor = 1
         const double safety = 0.9 * 1.0;
         double f = safety * pi_controller_raw(error_norm, has_prev_err, prev_err, o.pi_control_integral, o.pi_control_proportional, kErkOrder + 1, det);
@@ -208,6 +323,12 @@ DSH_UNROLL_N
     {
 DSH_UNROLL_N
       for (int r = 0; r < N; ++r) { old_y[r] = y[r]; y[r] = sy[r]; dy[r] = sdy[r]; }
+      if constexpr (SENS) {
+#pragma unroll
+        for (int j = 0; j < NP; ++j)
+DSH_UNROLL_N
+          for (int r = 0; r < N; ++r) { old_s[j][r] = s[j][r]; s[j][r] = ss[j][r]; ds[j][r] = sds[j][r]; }
+      }
       const double nt = t + hh;
       old_t = t;
       t = nt;
@@ -232,7 +353,19 @@ DSH_UNROLL_N
     } else
     while (col < C.n_eval && t_eval[col] <= upto) {
       double yv[N];
-      interpolate(t_eval[col], yv);
+      if constexpr (!SENS) interpolate(t_eval[col], yv);
+      else {  // interpolate_sens_inplace (:1237-1309): one beta function for the state, old_state.s_j and sdiff_j
+        double bf[S];
+        erk_beta_function(t, old_t, t_eval[col], bf);
+        erk_from_diff<N>(bf, old_y, diff, yv);
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+          double sv[N];
+          erk_from_diff<N>(bf, old_s[j], sdiff[j], sv);
+DSH_UNROLL_N
+          for (int i = 0; i < N; ++i) if (active) T.sens_out[(((int64_t)col * NP + j) * N + i) * nb + b] = sv[i];
+        }
+      }
 DSH_UNROLL_N
       for (int i = 0; i < N; ++i) if (active) y_out[((int64_t)col * N + i) * nb + b] = yv[i];
       col++;
@@ -256,6 +389,12 @@ DSH_UNROLL_N
     for (; col < C.n_eval; ++col) {  // columns that were never reached (root stop or error exit): NaN
 DSH_UNROLL_N
       for (int i = 0; i < N; ++i) y_out[((int64_t)col * N + i) * nb + b] = __builtin_nan("");
+      if constexpr (SENS) {
+#pragma unroll
+        for (int j = 0; j < NP; ++j)
+DSH_UNROLL_N
+          for (int i = 0; i < N; ++i) T.sens_out[(((int64_t)col * NP + j) * N + i) * nb + b] = __builtin_nan("");
+      }
     }
     if (status_out != nullptr) status_out[b] = status;
     if (t_root_out != nullptr) t_root_out[b] = root_idx >= 0 ? t_root : __builtin_nan("");

@@ -37,10 +37,28 @@ int erk_model_has_resident(int model, int64_t size) {
   });
   return ok ? 1 : 0;
 }
+// Tsit45 with forward sensitivities (k_erk_resident<.., SENS = true>): the models above that carry parameter derivatives, have no root functions and keep
+// N (14 + 12 NP) <= 112 doubles per lane (erk_sens_admitted, dsh_erk_kernel.hpp)
+template <class Mdl> constexpr bool erk_sens_ok() {
+  if constexpr (model_has_sens<Mdl>::value) return Mdl::N <= 4 && !Mdl::HAS_MASS && !model_has_reset<Mdl>::value && Mdl::NROOTS == 0 && erk_sens_admitted(Mdl::N, Mdl::NP);
+  else return false;
+}
+int erk_model_has_sens(int model, int64_t size) {
+  if (!erk_model_has_resident(model, size)) return 0;
+  if (is_jit_model(model)) {
+    const JitInfo* ji = jit_info(model);
+    if (!ji) return 0;
+    return (ji->has_sens && ji->nroots == 0 && erk_sens_admitted(ji->n, ji->np)) ? 1 : 0;
+  }
+  bool ok = false;
+  dispatch_static_model(model, size, [&](auto mdl) { ok = erk_sens_ok<decltype(mdl)>(); });
+  return ok ? 1 : 0;
+}
 }  // namespace dsh
 
 namespace {
 struct ErkStepsSpec { double* t_out; int64_t cap; };
+struct ErkSensSpec { double* out; double rtol; const double* atol_host; int64_t natol; };
 
 // why a model is refused, in the caller's words
 int erk_refuse(int model, int64_t size) {
@@ -55,10 +73,21 @@ int erk_refuse(int model, int64_t size) {
             "banded lane-per-member, wavefront-per-member and workgroup-per-member forms (n > 8) are not provided: use BDF, TR-BDF2 or ESDIRK34 for this model");
   return DSH_E_UNSUPPORTED;
 }
+// a model the plain kernel takes, refused with forward sensitivities
+int erk_refuse_sens(int model, int64_t size) {
+  int64_t n = 0, np = 0, nroots = 0;
+  int has_mass = 0;
+  (void)dsh_model_info(model, size, &n, &np, &has_mass, &nroots);
+  set_error("dsh_erk_solve_resident_sens: Tsit45 integrates forward sensitivities register-resident only — models with parameter derivatives, without root functions "
+            "(stop conditions), whose states and parameters satisfy nstates * (14 + 12 * nparams) <= 112 doubles per member (for example 2 states and up to 3 parameters, "
+            "4 states and 1 parameter, 1 state and up to 8 parameters); this model has " + std::to_string(n) + " states, " + std::to_string(np) + " parameters (" +
+            std::to_string(n * (14 + 12 * np)) + " doubles) and " + std::to_string(nroots) + " root functions: use BDF, TR-BDF2 or ESDIRK34 for its sensitivities");
+  return DSH_E_UNSUPPORTED;
+}
 
 int erk_solve_resident_impl(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol, double t0,
                             double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double* y_out, int32_t* stats, int32_t* status,
-                            double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host, const ErkStepsSpec* steps) {
+                            double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host, const ErkStepsSpec* steps, const ErkSensSpec* sens = nullptr) {
   DSH_REQUIRE(ctx != nullptr, "ctx is null");
   DSH_REQUIRE(method == 3, "method must be 3 (Tsit45)");
   DSH_REQUIRE(n_eval >= 1 && t_eval_host != nullptr, "t_eval must hold at least one time");
@@ -66,6 +95,7 @@ int erk_solve_resident_impl(dsh_ctx* ctx, int method, int model, int64_t size, i
   for (int64_t q = 0; q + 1 < n_eval; ++q) DSH_REQUIRE(t_eval_host[q] <= t_eval_host[q + 1], "t_eval must be increasing (InvalidTEval)");
   DSH_REQUIRE(t_eval_host[0] >= t0, "t_eval[0] before t0 (InvalidTEval)");
   if (!erk_model_has_resident(model, size)) return erk_refuse(model, size);
+  if (sens && !erk_model_has_sens(model, size)) return erk_refuse_sens(model, size);
   if (nb == 0) return DSH_OK;
   ErkConsts T;
   std::memset((void*)&T, 0, sizeof T);
@@ -76,6 +106,14 @@ int erk_solve_resident_impl(dsh_ctx* ctx, int method, int model, int64_t size, i
   // ExplicitRkConfig::default() (config.rs:141-160): NOT the BDF / SDIRK bounds dsh_adaptive_options carries
   T.min_shrink = 0.5; T.max_shrink = 1.0; T.min_growth = 1.0; T.max_growth = 2.0;
   if (steps) { T.steps_t_out = steps->t_out; T.steps_cap = (int)steps->cap; }
+  if (sens) {  // as dsh_sdirk_solve_resident_sens (admitted models have at most 4 states)
+    T.sens_out = sens->out; T.sens_rtol = sens->rtol; T.sens_error_control = sens->natol > 0 ? 1 : 0;
+    int64_t ns = 0, npar_ = 0, nroots_ = 0; int hm_ = 0;
+    if (dsh_model_info(model, size, &ns, &npar_, &hm_, &nroots_) != DSH_OK) return DSH_E_INVALID;
+    DSH_REQUIRE(sens->natol == 0 || sens->natol == 1 || sens->natol == ns, "sens_atol must have length 1 or nstates");
+    T.sens_pad = sens->natol <= 1 ? 1 : 0;  // 1: sens_atol[0] for every state
+    for (int64_t i = 0; i < 4 && i < ns; ++i) T.sens_atol[i] = sens->natol == 0 ? 0.0 : (sens->natol == 1 ? sens->atol_host[0] : sens->atol_host[i]);
+  }
   double* t_eval_dev = nullptr;
   unsigned long long* totals_dev = nullptr;
   ErkConsts* consts_dev = nullptr;
@@ -92,10 +130,22 @@ int erk_solve_resident_impl(dsh_ctx* ctx, int method, int model, int64_t size, i
   const dim3 grid((unsigned)((nb + 63) / 64)), blk(64);  // 64 members per wavefront in both modes
   DSH_HIP_CHECK(timing_begin(ctx));
   if (is_jit_model(model)) {
-    const std::string name = std::string("dsh::k_erk_resident<dsh::JitModel, ") + (ba ? "true" : "false") + ", " + (wave ? "true" : "false") + ">";
+    const std::string name = std::string("dsh::k_erk_resident<dsh::JitModel, ") + (ba ? "true" : "false") + ", " + (wave ? "true" : "false") + (sens ? ", true>" : ">");
     rc = jit_launch(ctx, model, "dsh_erk_kernel.hpp", name, {name}, name, grid, blk, 0, nb, p, atol, (const ErkConsts*)consts_dev, (const double*)t_eval_dev, y_out, stats,
                     status, t_root, root_idx, ncols, totals_dev);
     if (rc != DSH_OK) return rc;
+  } else if (sens) {
+    dispatch_static_model(model, size, [&](auto mdl) {
+      using Mdl = decltype(mdl);
+      if constexpr (erk_sens_ok<Mdl>()) {
+#define DSH_ERK_SENS_LAUNCH(BA, WAVE)                                                                                                                         \
+  hipLaunchKernelGGL((k_erk_resident<Mdl, BA, WAVE, true>), grid, blk, 0, ctx->stream, nb, p, atol, (const ErkConsts*)consts_dev, (const double*)t_eval_dev, \
+                     y_out, stats, status, t_root, root_idx, ncols, totals_dev)
+        if (ba) { if (wave) DSH_ERK_SENS_LAUNCH(true, true); else DSH_ERK_SENS_LAUNCH(true, false); }
+        else { if (wave) DSH_ERK_SENS_LAUNCH(false, true); else DSH_ERK_SENS_LAUNCH(false, false); }
+#undef DSH_ERK_SENS_LAUNCH
+      }
+    });
   } else
   dispatch_static_model(model, size, [&](auto mdl) {
     using Mdl = decltype(mdl);
@@ -130,6 +180,20 @@ int dsh_erk_solve_resident(dsh_ctx* ctx, int method, int model, int64_t size, in
   DSH_ENTER(ctx);
   return erk_solve_resident_impl(ctx, method, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, t_eval_host, n_eval, y_out, stats, status, t_root, root_idx, ncols,
                                  totals_host, nullptr);
+}
+// 1 when dsh_erk_solve_resident_sens takes the model: see erk_model_has_sens above
+int dsh_erk_model_has_sens(int model, int64_t size) { return erk_model_has_sens(model, size); }
+// Tsit45 with forward sensitivities in the same launch (problem.tsit45_sens(); arguments as dsh_sdirk_solve_resident_sens, method = 3): sens_out n_eval x np x n x nb,
+// nsens_atol = 0 leaves the sensitivities out of the error control.  A model outside dsh_erk_model_has_sens: DSH_E_UNSUPPORTED.
+int dsh_erk_solve_resident_sens(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol, double t0,
+                                double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double sens_rtol, const double* sens_atol_host,
+                                int64_t nsens_atol, double* y_out, double* sens_out, int32_t* stats, int32_t* status, int64_t* totals_host) {
+  DSH_ENTER(ctx);
+  DSH_REQUIRE(sens_out != nullptr, "sens_out is null");
+  DSH_REQUIRE(nsens_atol == 0 || sens_atol_host != nullptr, "sens_atol is null");
+  const ErkSensSpec sp{sens_out, sens_rtol, sens_atol_host, nsens_atol};
+  return erk_solve_resident_impl(ctx, method, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, t_eval_host, n_eval, y_out, stats, status, nullptr, nullptr, nullptr,
+                                 totals_host, nullptr, &sp);
 }
 // OdeSolverMethod::solve (method.rs:227-258 over :881-961) inside the launch: the state after every accepted step of every member (arguments as
 // dsh_sdirk_solve_resident_steps)

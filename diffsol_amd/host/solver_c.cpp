@@ -49,6 +49,7 @@ struct dshs_solver {
       if (!problem.eqn->registry_model(&m, &sz) || !dsh_model_has_resident(3, m, sz))
         throw LaError(DSH_E_UNSUPPORTED, "Tsit45 runs register-resident only — built-in static models with n <= 4, DiffSL models in the static form with n <= 8, no reset operator; "
                                          "banded lane-per-member, wavefront-per-member and workgroup-per-member forms (n > 8) are not provided: use BDF, TR-BDF2 or ESDIRK34 for this model");
+      if (problem.sens && !dsh_erk_model_has_sens(m, sz)) throw LaError(DSH_E_UNSUPPORTED, tsit45_sens_refusal(*problem.eqn));
       fused = false;
       solver = std::move(k);
     } else {
@@ -127,7 +128,7 @@ ResidentPick pick_resident(const dshs_solver* s, int group, bool for_auto = fals
   if (s->method == DSHS_METHOD_TSIT45) {  // one form only: the register-resident explicit kernel (dsh_erk_solve_resident); make_solver() checked the model
     int m = 0; int64_t sz = 0;
     r.method = 3;
-    if (!s->problem.sens && s->problem.eqn->registry_model(&m, &sz) && dsh_model_has_resident(3, m, sz)) { r.ok = true; r.model = m; r.size = sz; }
+    if (s->problem.eqn->registry_model(&m, &sz) && dsh_model_has_resident(3, m, sz) && (!s->problem.sens || dsh_erk_model_has_sens(m, sz))) { r.ok = true; r.model = m; r.size = sz; }
     return r;
   }
   if (s->problem.sens) {
@@ -436,6 +437,10 @@ void run_resident(dshs_solver* s, const double* t_eval, int64_t nt, int group, i
       rc = dsh_bdf_solve_wave_member_sens(c, model, size, nb, params_dev, s->problem.atol.ptr(), 1, s->problem.rtol, s->problem.t0, s->problem.h0, &o, t_eval, nt,
                                           s->problem.sens_rtol, sa.data(), (int64_t)sa.size(), out, (double*)(sorted ? sens_sorted : sens_dev), (int32_t*)stats_dev,
                                           (int32_t*)status_dev, totals);
+    else if (method == 3)
+      rc = dsh_erk_solve_resident_sens(c, method, model, size, nb, params_dev, s->problem.atol.ptr(), 1, s->problem.rtol, s->problem.t0, s->problem.h0, &o, t_eval, nt,
+                                       s->problem.sens_rtol, sa.data(), (int64_t)sa.size(), out, (double*)(sorted ? sens_sorted : sens_dev), (int32_t*)stats_dev,
+                                       (int32_t*)status_dev, totals);
     else if (method == 0)
       rc = dsh_bdf_solve_adaptive_sens(c, model, size, nb, params_dev, s->problem.atol.ptr(), 1, s->problem.rtol, s->problem.t0, s->problem.h0, &o, t_eval, nt,
                                        s->problem.sens_rtol, sa.data(), (int64_t)sa.size(), out, (double*)(sorted ? sens_sorted : sens_dev), (int32_t*)stats_dev,
@@ -653,6 +658,7 @@ int dshs_get_state(dshs_solver* s, double* t, double* h, int* order, double* y_h
 int64_t dshs_nparams(const dshs_solver* s) { return s->problem.eqn->nparams(); }
 int dshs_interpolate_sens(dshs_solver* s, double t, double* s_host) {
   return guarded_flushed(s, [&]() {
+    if (s->method == DSHS_METHOD_TSIT45 && s->problem.sens) throw LaError(DSH_E_UNSUPPORTED, kTsit45HostDriven);  // the sensitivities exist inside the resident launch only
     if ((!s->bdf && !s->sdirk) || !s->problem.sens) throw LaError(DSH_E_INVALID, "the solver was not created with forward sensitivities (dshs_create_sens)");
     const size_t len = (size_t)(s->problem.eqn->nstates() * s->ctx.nbatch());
     const std::vector<HipVec>& cur = s->bdf ? s->bdf->sens() : s->sdirk->sens();
@@ -876,9 +882,10 @@ int dshs_solve_adaptive(dshs_solver* s, double t_final, int64_t max_cols, int gr
                         int32_t* stats_host, int32_t* status_host, double* t_root_host, int32_t* root_idx_host, int64_t* totals) {
   return guarded_flushed(s, [&]() {
     if (!y_host || !t_host || !ncols_host || max_cols < 2) throw LaError(DSH_E_INVALID, "dshs_solve_adaptive: y_host, t_host, ncols_host and max_cols >= 2 are needed");
-    if (s->problem.sens) throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_adaptive: without forward sensitivities (dshs_solve walks the host-driven path for the rest)");
-    const ResidentPick pk = pick_resident(s, group);
     const bool erk = s->method == DSHS_METHOD_TSIT45;
+    // a Tsit45 solver with forward sensitivities has no host-driven path to send the caller to: it writes every step of the states (and no sensitivities)
+    if (s->problem.sens && !erk) throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_adaptive: without forward sensitivities (dshs_solve walks the host-driven path for the rest)");
+    const ResidentPick pk = pick_resident(s, group);
     const bool sdirk = s->method != DSHS_METHOD_BDF && !erk;  // TR-BDF2 / ESDIRK34
     if (!pk.ok || (!sdirk && !erk && !pk.wave_member && !dsh_model_has_adaptive_steps(pk.model, pk.size)))
       throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_adaptive: no device-resident integrator that writes every step for this model and method (register-resident static models, banded lane-per-member forms, "
@@ -960,7 +967,8 @@ int dshs_solve_dense_adaptive_sens(dshs_solver* s, const double* t_eval, int64_t
 static void solve_sens_outputs(dshs_solver* s, const double* t_eval, int64_t nt, int group, int deterministic_pow, double* y_host, double* sens_host, OutSensSpec& os,
                                int32_t* stats_host, int32_t* status_host, int64_t* totals) {
   const std::string fn = os.fn;
-  if (s->method == DSHS_METHOD_TSIT45) throw LaError(DSH_E_UNSUPPORTED, fn + ": Tsit45 has no forward sensitivities; use BDF, TR-BDF2 or ESDIRK34");
+  if (s->method == DSHS_METHOD_TSIT45 && !s->problem.sens)
+    throw LaError(DSH_E_UNSUPPORTED, fn + ": this Tsit45 solver was not created with forward sensitivities (dshs_create_sens)");
   if (!s->problem.sens) throw LaError(DSH_E_UNSUPPORTED, fn + ": the solver was not created with forward sensitivities (dshs_create_sens)");
   int64_t msize = 0, mn = 0, mnp = 0;
   if (!s->problem.eqn->registry_model(&os.model, &msize) || !dsh_model_has_out_sens(os.model))

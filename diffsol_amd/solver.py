@@ -70,7 +70,7 @@ class Solver:
         for k, v in (options or {}).items():
             setattr(o, k, v)
         h = vp()
-        if sens:  # problem.bdf_sens(): forward sensitivities integrated alongside (sens_atol None: not part of the error control)
+        if sens:  # problem.bdf_sens() / tr_bdf2_sens() / esdirk34_sens() / tsit45_sens(): forward sensitivities integrated alongside (sens_atol None: not part of the error control)
             sa = np.zeros(0) if sens_atol is None else np.ascontiguousarray(np.asarray(sens_atol, dtype=np.float64).reshape(-1))
             sa_buf = sa if sa.size else np.zeros(1)
             rc = L.dshs_create_sens(device, stream, model, model_size, nbatch, p.ctypes.data_as(_ffi.c_dp), p.size, rtol, a.ctypes.data_as(_ffi.c_dp), a.size,
@@ -266,7 +266,7 @@ class Solver:
         return y, t, m, dict(zip(self.ADAPTIVE_TOTALS, [int(v) for v in totals]))
 
     def solve_dense_adaptive_sens(self, t_eval, group=1, deterministic_pow=True, want_member_stats=False):
-        """solve_dense_sensitivities (sensitivities.rs:114-260) on the device-resident BDF with forward sensitivities (dshs_solve_dense_adaptive_sens): states AND
+        """solve_dense_sensitivities (sensitivities.rs:114-260) on the device-resident integrators with forward sensitivities — BDF, TR-BDF2, ESDIRK34, Tsit45 — (dshs_solve_dense_adaptive_sens): states AND
         the sensitivities of every parameter at t_eval from one launch; the solver must have been created with sens=True.
         Returns (y [nt, nbatch, n], sens [nparams, nt, nbatch, n], totals dict[, member dict(stats [5, nbatch], status)])."""
         te = np.ascontiguousarray(t_eval, dtype=np.float64)
@@ -373,3 +373,7 @@ class OdeBuilder:
     def tr_bdf2(self): return Solver(self._model, self._p, method=METHOD_TR_BDF2, **self._kw)
     def esdirk34(self): return Solver(self._model, self._p, method=METHOD_ESDIRK34, **self._kw)
     def tsit45(self): return Solver(self._model, self._p, method=METHOD_TSIT45, **self._kw)  # device-resident only: solve_dense / solve_dense_adaptive / solve_adaptive
+
+    def tsit45_sens(self, sens_rtol=None, sens_atol=None):
+        """problem.tsit45_sens(): solve_dense_adaptive_sens / solve_dense_sens_outputs / solve_dense_sens_fit; sens_atol None keeps the sensitivities out of the error control"""
+        return Solver(self._model, self._p, method=METHOD_TSIT45, sens=True, sens_rtol=sens_rtol, sens_atol=sens_atol, **self._kw)

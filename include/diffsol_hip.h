@@ -600,6 +600,16 @@ int dsh_erk_solve_resident(dsh_ctx* ctx, int method, int model, int64_t size, in
 int dsh_erk_solve_resident_steps(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol,
                                  double t0, double h0, const dsh_adaptive_options* opts, double t_final, int64_t max_cols, double* y_out, double* t_out, int32_t* stats,
                                  int32_t* status, double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host);
+/* Tsit45 with FORWARD SENSITIVITIES of every parameter in the same launch (problem.tsit45_sens(): ExplicitRk<.., SensEquations>, explicit_rk.rs:46-54; the Rk core's
+ * sensitivity halves runge_kutta.rs:518-522, :578-607, :812-822, :1237-1309), everything in registers.  Models (dsh_erk_model_has_sens): those of
+ * dsh_model_has_resident(3, ..) that carry parameter derivatives, have no root functions and satisfy nstates * (14 + 12 * nparams) <= 112 (doubles a member keeps:
+ * 2 states with up to 3 parameters, 4 states with 1, 1 state with up to 8); any other model: DSH_E_UNSUPPORTED.  Arguments as dsh_sdirk_solve_resident_sens with
+ * method = 3: sens_out n_eval x np x n x nb (device, batch-fastest; columns a member never reached are NaN), sens_atol of length 1 or n, nsens_atol = 0 keeps the
+ * sensitivities out of the error test. */
+int dsh_erk_model_has_sens(int model, int64_t size);
+int dsh_erk_solve_resident_sens(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol,
+                                double t0, double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double sens_rtol,
+                                const double* sens_atol_host, int64_t nsens_atol, double* y_out, double* sens_out, int32_t* stats, int32_t* status, int64_t* totals_host);
 
 
 /* ------------------------------------------------------------------------------------------------------------------------------------------------

@@ -27,7 +27,10 @@ typedef struct dsh_ctx dsh_ctx; /* include/diffsol_hip.h */
  * include/diffsol_hip.h): dshs_solve_dense in the ensemble modes auto / per member / wavefront, dshs_solve_dense_adaptive and dshs_solve_adaptive integrate it; the
  * host-driven entries (dshs_step, dshs_set_stop_time, dshs_interpolate, dshs_solve, dshs_solve_to_points, DSHS_ENSEMBLE_LOCKSTEP) return DSH_E_UNSUPPORTED with a message
  * that names the entries that work.  dshs_create refuses (DSH_E_UNSUPPORTED) a model with a mass matrix — MassMatrixNotSupported, as the reference does —, a model
- * without a register-resident form (n > 8, run-time-sized, reset operator) and, through dshs_create_sens, forward sensitivities. */
+ * without a register-resident form (n > 8, run-time-sized, reset operator).  dshs_create_sens (problem.tsit45_sens()) takes the models of dsh_erk_model_has_sens —
+ * parameter derivatives, no stop conditions, nstates * (14 + 12 * nparams) <= 112 — and refuses every other one the same way; dshs_solve_dense_adaptive_sens,
+ * dshs_solve_dense_sens_out and dshs_solve_dense_sens_fit then integrate the sensitivities inside the launch (dsh_erk_solve_resident_sens), dshs_solve_adaptive
+ * writes the states of every step and no sensitivities, dshs_interpolate_sens stays host-driven and refused. */
 #define DSHS_METHOD_TSIT45 3
 
 #define DSHS_STOP_INTERNAL_TIMESTEP 0 /* OdeSolverStopReason, crates/diffsol/src/ode_solver/method.rs:22-40 */
@@ -188,7 +191,7 @@ int dshs_solve_dense_adaptive_sens(dshs_solver* s, const double* t_eval, int64_t
  * launch (dsh_model_out_sens) maps them to the outputs, and only out / dout are copied back (y_host / sens_host too when they are not NULL: [nt][b][state],
  * [nparams][nt][b][state]).  Otherwise (DAEs, models without such an integrator) the host-driven solver is stepped and interpolated at the save points (group and
  * deterministic_pow are not used) and the collected columns go through the same launch.  out_host: [nt][b][nout]; dout_host: [nparams][nt][b][nout].
- * DSH_E_UNSUPPORTED: no sensitivities, no output-sensitivity source, Tsit45, a reset_i, a stop condition that fires before the last save point.
+ * DSH_E_UNSUPPORTED: no sensitivities, no output-sensitivity source, a Tsit45 solver created without sensitivities, a reset_i, a stop condition that fires before the last save point.
  * stats_host / status_host / totals as dshs_solve_dense_adaptive (host-driven: the lock-step solver's counters for every member, status 0). */
 int dshs_solve_dense_sens_out(dshs_solver* s, const double* t_eval, int64_t nt, int group /* 1 | 64 */, int deterministic_pow, double* y_host, double* sens_host,
                               double* out_host, double* dout_host, int32_t* stats_host, int32_t* status_host, int64_t* totals);

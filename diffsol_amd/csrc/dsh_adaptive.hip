@@ -99,6 +99,31 @@ bool adaptive_fast_launch(int model, int64_t size, bool ba, bool wave, const dsh
                           const double* atol, const AdaptiveConsts* consts, const double* t_eval, double* y_out, int32_t* stats, int32_t* status, double* t_root,
                           int32_t* root_idx, int32_t* ncols, unsigned long long* totals);  // dsh_adaptive_fast.hip
 }
+#if DSH_WAVE_TIMELINE
+// Diagnostic build (scripts/wave_timeline.py): one device buffer for the records of the newest launch, one record per wavefront; kept for the life of the process.
+namespace {
+dsh::WaveTimelineRecord* g_wave_timeline = nullptr;
+int64_t g_wave_timeline_cap = 0, g_wave_timeline_n = 0;
+dsh::WaveTimelineRecord* wave_timeline_buffer(int64_t waves) {
+  if (waves > g_wave_timeline_cap) {
+    if (g_wave_timeline) (void)hipFree(g_wave_timeline);
+    g_wave_timeline = nullptr; g_wave_timeline_cap = 0;
+    if (hipMalloc((void**)&g_wave_timeline, sizeof(dsh::WaveTimelineRecord) * (size_t)waves) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    g_wave_timeline_cap = waves;
+  }
+  g_wave_timeline_n = waves;
+  return g_wave_timeline;
+}
+}  // namespace
+// the records of the newest dsh_bdf_solve_adaptive launch -> host; returns how many (at most max_records), -1 on error
+extern "C" int64_t dsh_wave_timeline_read(void* host, int64_t max_records) {
+  if (!g_wave_timeline || !host) return -1;
+  const int64_t n = g_wave_timeline_n < max_records ? g_wave_timeline_n : max_records;
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  if (hipMemcpy(host, g_wave_timeline, sizeof(dsh::WaveTimelineRecord) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  return n;
+}
+#endif
 namespace {
 struct SensSpec { double* out; double rtol; const double* atol_host; int64_t natol; };  // forward sensitivities of dsh_bdf_solve_adaptive_sens
 // does the static model have a device-resident BDF with forward sensitivities?  (sens_mul / init_sens_mul, identity mass, no root functions, n <= 4)
@@ -203,6 +228,10 @@ int bdf_solve_adaptive_impl(dsh_ctx* ctx, int model, int64_t size, int64_t nb, c
     C.r.member_lanes = (C.r.o.group == 1 && !is_jit_model(model) && !sens && !steps) ? member_lanes_env : 0;
   }
   if (steps) { C.steps_t_out = steps->t_out; C.steps_cap = (int)steps->cap; }
+  C.simds = 4 * ctx->num_cu;  // the lock-step fast kernel's priority policy runs in launches with more wavefronts than this (DSH_PAIR_PRIO, dsh_adaptive_kernel.hpp)
+#if DSH_WAVE_TIMELINE
+  C.timeline = wave_timeline_buffer((nb + 63) / 64);
+#endif
   if (sens) {
     C.sens_out = sens->out; C.sens_rtol = sens->rtol; C.sens_error_control = sens->natol > 0 ? 1 : 0;
     int64_t ns = 0, npar_ = 0, nroots_ = 0; int hm_ = 0;

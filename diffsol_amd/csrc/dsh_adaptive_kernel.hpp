@@ -9,6 +9,12 @@ namespace dsh {
 constexpr int kMaxOrder = 5;
 constexpr int kNC = kMaxOrder + 3;  // columns of the difference array
 
+// Diagnostic build (scripts/wave_timeline.py, profiles/wave_pairing.md): lane 0 of every wavefront of the lock-step fast kernel stores where and when it ran.
+// 0: no field, no stamp, no store — the kernel and AdaptiveConsts of the library.
+#ifndef DSH_WAVE_TIMELINE
+#define DSH_WAVE_TIMELINE 0
+#endif
+
 struct AdaptiveConsts {
   ResidentConsts r;
   double alpha[6], gamma[6], ec2[6];  // Bdf::_new tables (bdf.rs:286-306), computed on the host
@@ -34,7 +40,19 @@ struct AdaptiveConsts {
   // y_out [steps_cap][N][nb] and steps_t_out [steps_cap][nb]; ncols_out = the columns the member produced (columns beyond steps_cap are counted, not stored).
   double* steps_t_out;
   int steps_cap, steps_pad;
+  // SIMDs of the device, 4 x CUs: a launch with more wavefronts than that puts two on some SIMDs, and the lock-step fast kernel then runs its priority policy
+  // (DSH_PAIR_PRIO below).  Appended: no other offset moves.
+  int simds, simds_pad;
+#if DSH_WAVE_TIMELINE
+  struct WaveTimelineRecord* timeline;  // diagnostic build only (scripts/wave_timeline.py): one record per wavefront of the lock-step fast kernel
+#endif
 };
+#if DSH_WAVE_TIMELINE
+struct WaveTimelineRecord {
+  unsigned long long t_in, t_out;  // s_memrealtime (100 MHz) at entry and after the last step
+  unsigned int block, hw_id, xcc_id, n_steps, n_newton, pad;
+};
+#endif
 constexpr int kSegDbl = 128, kSegInt = 32;  // slots per member (upper bounds for n <= 4)
 
 // The solver options the BODY of k_bdf_adaptive reads through `o`, each with the value dsh_adaptive_default_options() gives it: the ONE list behind that function
@@ -273,6 +291,31 @@ __device__ __forceinline__ double inv_root_2k_group(double x, int k, double expo
 #ifndef DSH_ADAPTIVE_DT_PRIVATE
 #define DSH_ADAPTIVE_DT_PRIVATE 0
 #endif
+// Issue priority where two lock-step groups share a SIMD (LOCKFAST in k_bdf_adaptive; profiles/wave_pairing.md).  At equal priority the SIMD issues the older
+// wavefront's instructions first and the younger takes the slots that are left, so of two groups on a SIMD one runs almost as if alone and the other waits for it;
+// the launch lasts until the other has caught up alone (measured: the first arrival at 1.00 of a lone wavefront's time per Newton iteration, the second at 1.30).
+// The policy runs in launches with more wavefronts than the device has SIMDs (AdaptiveConsts::simds) and at most twice as many: two rounds, all resident from the
+// start; a launch that fits on the SIMDs, or one with later rounds, executes no s_setprio.  The wavefronts of
+// the dispatch's first round (blockIdx.x < simds: the first arrivals, measured) stay at priority 0 and win the ties by age.  Those of the second round change theirs
+// at the head of the step loop: 1 for the first DSH_PAIR_PRIO_HIGH of every 2 x DSH_PAIR_PRIO_PERIOD trips (a power of two), 0 for the rest, so each of the two is
+// ahead of its partner for a part of its life.  A wavefront passes its trips at priority faster than the others, so equal TRIPS at 1 and 0 would be unequal TIMES:
+// with the partner at 0.70 of the rate, 1 / 1.70 = 0.59 of the trips at 1 make the times equal; 5 of 8 measured best.
+// DSH_PAIR_PRIO_HIGH=0 is the symmetric form, both rounds alternating 0 / 1 every DSH_PAIR_PRIO_PERIOD trips in opposite phase: half the gain, the first arrival
+// still ahead.  Timing only: no value depends on the policy (tests/test_gpu_pair_priority.py).  DSH_PAIR_PRIO=0: the instructions of the kernel without it.
+#ifndef DSH_PAIR_PRIO
+#define DSH_PAIR_PRIO 1
+#endif
+#ifndef DSH_PAIR_PRIO_PERIOD
+#define DSH_PAIR_PRIO_PERIOD 4
+#endif
+#ifndef DSH_PAIR_PRIO_HIGH
+#define DSH_PAIR_PRIO_HIGH 5
+#endif
+// the phase of the policy is wavefront-uniform by construction; s_setprio ignores EXEC, so each one sits alone behind a scalar branch on a readfirstlane value
+__device__ __forceinline__ void pair_prio_set(unsigned phase_bits) {
+  if (__builtin_amdgcn_readfirstlane(phase_bits & 1u) != 0) __builtin_amdgcn_s_setprio(1);
+  else __builtin_amdgcn_s_setprio(0);
+}
 // FAST (dsh_adaptive_options::deterministic_pow == 2, the default arithmetic of Solver.solve_dense; instantiated only in dsh_adaptive_fast.hip, which is compiled with -ffp-contract=fast and
 // reciprocal-math division): ocml's pow (the Newton chain's two fixed-exponent powers by pow_p08 / root_k above), fused multiply-adds, the Newton norm's weights as
 // reciprocals computed once per solve.  NOT bit-comparable with the oracle: held to 1e-6 relative on the states at tight tolerances (tests/test_gpu_adaptive.py).
@@ -292,6 +335,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DSH_ADAPTIVE
   static_assert(!LOCKFAST || (!SEG && !SENS), "decisions by ballot: lock-step groups of the plain fast kernel");
   constexpr bool kLit = DSH_ORDER_PATHS_LITERALS != 0;  // per-order bodies (with_order above): the order's coefficients as constants
   const AdaptiveConsts& C = *Cp;
+  constexpr bool kPairPrio = LOCKFAST && DSH_PAIR_PRIO != 0;
+  static_assert((DSH_PAIR_PRIO_PERIOD & (DSH_PAIR_PRIO_PERIOD - 1)) == 0 && DSH_PAIR_PRIO_PERIOD > 0, "DSH_PAIR_PRIO_PERIOD: a power of two");
+  static_assert(DSH_PAIR_PRIO_HIGH >= 0 && DSH_PAIR_PRIO_HIGH < 2 * DSH_PAIR_PRIO_PERIOD, "DSH_PAIR_PRIO_HIGH: trips of the 2 x DSH_PAIR_PRIO_PERIOD");
+  // the wavefront's role in the policy (DSH_PAIR_PRIO above): 0 = no policy in this launch, no s_setprio; 1 = a wavefront of the first round of the dispatch (the
+  // first arrivals); 2 = of the second.  Scalar.  The policy is for launches of two rounds, all wavefronts resident from the start.  With further rounds the next
+  // wavefront starts when one ends, and there a first arrival that ends early is what keeps the SIMD full: measured 15 % SLOWER with the policy at three rounds.
+  unsigned pair_mode = 0;
+  if constexpr (kPairPrio) {
+    const uint64_t simds = (uint64_t)(C.simds > 0 ? C.simds : 0), waves = (uint64_t)(nb + 63) / 64u;
+    if (waves > simds && waves <= 2u * simds) pair_mode = blockIdx.x >= simds ? 2u : 1u;
+    pair_mode = (unsigned)__builtin_amdgcn_readfirstlane((int)pair_mode);
+  }
+#if DSH_WAVE_TIMELINE
+  if constexpr (LOCKFAST) {
+    const unsigned long long t_in = __builtin_amdgcn_s_memrealtime();
+    if (threadIdx.x == 0 && C.timeline != nullptr) {
+      WaveTimelineRecord& w = C.timeline[blockIdx.x];
+      w.t_in = t_in; w.block = blockIdx.x;
+      w.hw_id = __builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_REG_HW_ID, all 32 bits
+      w.xcc_id = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // HW_REG_XCC_ID
+    }
+  }
+#endif
   const int ML = (!WAVE && !SEG && C.r.member_lanes > 0) ? C.r.member_lanes : 64;  // members per wavefront under per-member control (see ResidentConsts)
   const int64_t bglobal = (int64_t)blockIdx.x * ML + threadIdx.x;
   const bool active = (int)threadIdx.x < ML && bglobal < nb;  // the other lanes shadow a live member (no stores) so that the whole wavefront reaches every reduction
@@ -778,6 +844,13 @@ DSH_UNROLL_N
   int seg_trips = 0;
   while (!done) {
     if (++guard > o.max_steps) { status = kRsMaxStepsExceeded; break; }
+    if constexpr (kPairPrio) {  // DSH_PAIR_PRIO above
+      if constexpr (DSH_PAIR_PRIO_HIGH > 0) {
+        if (pair_mode == 2u) pair_prio_set(((unsigned)(guard - 1) & (2u * DSH_PAIR_PRIO_PERIOD - 1u)) < (unsigned)DSH_PAIR_PRIO_HIGH ? 1u : 0u);
+      } else {
+        if (pair_mode != 0u) pair_prio_set((unsigned)((unsigned long long)(guard - 1) / DSH_PAIR_PRIO_PERIOD) + pair_mode - 1u);
+      }
+    }
     // ================================================================ Bdf::step (bdf.rs:1277-1589)
     double safety = 0.0, error_norm = 0.0;
     const int old_err_fails = n_err_fails;
@@ -1429,6 +1502,15 @@ DSH_UNROLL_N
       if (!C.seg_last && (col >= C.seg_col_end || (C.seg_step_budget > 0 && ++seg_trips >= C.seg_step_budget))) break;
     }
   }
+#if DSH_WAVE_TIMELINE
+  if constexpr (LOCKFAST) {
+    const unsigned long long t_out = __builtin_amdgcn_s_memrealtime();
+    if (threadIdx.x == 0 && C.timeline != nullptr) {
+      WaveTimelineRecord& w = C.timeline[blockIdx.x];
+      w.t_out = t_out; w.n_steps = (unsigned)n_steps; w.n_newton = (unsigned)n_newton; w.pad = 0u;
+    }
+  }
+#endif
   if constexpr (SEG) {
     if (status != kRsOk) done = true;
     if (active) {

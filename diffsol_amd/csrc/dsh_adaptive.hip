@@ -25,16 +25,12 @@
 // Scope: static register models (n <= 4), with or without mass matrix (consistent initialisation on the device) and root functions
 // (per-member event stops); shared pieces in dsh_resident.hpp, the (E)SDIRK counterpart in dsh_sdirk_resident.hip.
 #include <cmath>
-#include <cstdio>
-#include <vector>
-
+#include <cstdlib>
 #include <cstring>
-#include <map>
-#include <mutex>
+#include <string>
 #include <vector>
 
-#include "dsh_internal.hpp"
-#include "dsh_resident.hpp"
+#include "dsh_resident_host.hpp"
 
 // DSH_EXPERIMENTS (compile time, `make EXPERIMENTS=1`; off in the shipped library): the variants that were built, verified bit-identical and MEASURED SLOWER than
 // what ships — re-binning between segments of a per-member run (DSH_REBIN / DSH_REBIN_STEPS: 10.3 - 19 ms against 8.4 ms, profiles/r03_rebin.txt) and the
@@ -125,16 +121,12 @@ extern "C" int64_t dsh_wave_timeline_read(void* host, int64_t max_records) {
 }
 #endif
 namespace {
-struct SensSpec { double* out; double rtol; const double* atol_host; int64_t natol; };  // forward sensitivities of dsh_bdf_solve_adaptive_sens
 // does the static model have a device-resident BDF with forward sensitivities?  (sens_mul / init_sens_mul, identity mass, no root functions, n <= 4)
 template <class Mdl> constexpr bool adaptive_sens_ok() {
   if constexpr (model_has_sens<Mdl>::value) return Mdl::N <= 4 && !Mdl::HAS_MASS && Mdl::NROOTS == 0 && model_band_k<Mdl>::value == 0;
   else return false;
 }
-struct StepsSpec { double* t_out; int64_t cap; };  // OdeSolverMethod::solve: every accepted step out (AdaptiveConsts::steps_cap)
-int bdf_solve_adaptive_impl(dsh_ctx* ctx, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol, double t0,
-                            double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double* y_out, int32_t* stats, int32_t* status,
-                            double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host, const SensSpec* sens, const StepsSpec* steps = nullptr);
+int bdf_solve_adaptive_impl(const SolveArgs& a);
 }  // namespace
 extern "C" {
 // hybrid models whose events are handled INSIDE dsh_bdf_solve_adaptive (move back to the root, apply the reset, restart at first order, go on to the last save
@@ -169,7 +161,7 @@ int dsh_bdf_solve_adaptive(dsh_ctx* ctx, int model, int64_t size, int64_t nb, co
                            double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double* y_out, int32_t* stats, int32_t* status,
                            double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host) {
   DSH_ENTER(ctx);
-  return bdf_solve_adaptive_impl(ctx, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, t_eval_host, n_eval, y_out, stats, status, t_root, root_idx, ncols, totals_host, nullptr);
+  return bdf_solve_adaptive_impl({ctx, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, t_eval_host, n_eval, y_out, stats, status, t_root, root_idx, ncols, totals_host, nullptr, nullptr});
 }
 int dsh_bdf_solve_adaptive_sens(dsh_ctx* ctx, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol, double t0,
                                 double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double sens_rtol, const double* sens_atol_host,
@@ -182,7 +174,7 @@ int dsh_bdf_solve_adaptive_sens(dsh_ctx* ctx, int model, int64_t size, int64_t n
     return DSH_E_UNSUPPORTED;
   }
   const SensSpec sp{sens_out, sens_rtol, sens_atol_host, nsens_atol};
-  return bdf_solve_adaptive_impl(ctx, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, t_eval_host, n_eval, y_out, stats, status, nullptr, nullptr, nullptr, totals_host, &sp);
+  return bdf_solve_adaptive_impl({ctx, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, t_eval_host, n_eval, y_out, stats, status, nullptr, nullptr, nullptr, totals_host, &sp, nullptr});
 }
 // OdeSolverMethod::solve (method.rs:227-258 over :881-961) inside the launch: the register-resident kernels only (static models, built-in or run-time-compiled)
 int dsh_model_has_adaptive_steps(int model, int64_t size) {
@@ -201,106 +193,49 @@ int dsh_bdf_solve_adaptive_steps(dsh_ctx* ctx, int model, int64_t size, int64_t 
     return DSH_E_UNSUPPORTED;
   }
   const StepsSpec st{t_out, max_cols};
-  return bdf_solve_adaptive_impl(ctx, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, &t_final, 1, y_out, stats, status, t_root, root_idx, ncols, totals_host, nullptr, &st);
+  return bdf_solve_adaptive_impl({ctx, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, &t_final, 1, y_out, stats, status, t_root, root_idx, ncols, totals_host, nullptr, &st});
 }
 }  // extern "C"
 namespace {
-int bdf_solve_adaptive_impl(dsh_ctx* ctx, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol, double t0,
-                            double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double* y_out, int32_t* stats, int32_t* status,
-                            double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host, const SensSpec* sens, const StepsSpec* steps) {
-  DSH_REQUIRE(ctx != nullptr, "ctx is null");
-  DSH_REQUIRE(n_eval >= 1 && t_eval_host != nullptr, "t_eval must hold at least one time");
-  DSH_REQUIRE(atol_nb == 1 || atol_nb == nb, "atol must be broadcast (nbatch 1) or per member");
-  for (int64_t k = 0; k + 1 < n_eval; ++k) DSH_REQUIRE(t_eval_host[k] <= t_eval_host[k + 1], "t_eval must be increasing (InvalidTEval)");
-  DSH_REQUIRE(t_eval_host[0] >= t0, "t_eval[0] before t0 (InvalidTEval)");
+int bdf_solve_adaptive_impl(const SolveArgs& a) {
+  static const char* const who = "dsh_bdf_solve_adaptive";
+  if (const int rc = check_solve_args(a, who); rc != DSH_OK) return rc;
+  dsh_ctx* const ctx = a.ctx;
+  const int model = a.model;
+  const int64_t size = a.size, nb = a.nb;
+  const double *const p = a.p, *const atol = a.atol;
+  double *const y_out = a.y_out, *const t_root = a.t_root;
+  int32_t *const stats = a.stats, *const status = a.status, *const root_idx = a.root_idx, *const ncols = a.ncols;
+  const bool sens = a.sens != nullptr;
   if (!dsh_model_has_adaptive(model, size)) { set_error("dsh_bdf_solve_adaptive: model has no device-resident kernel (needs a static model, n <= 4)"); return DSH_E_UNSUPPORTED; }
   if (nb == 0) return DSH_OK;
   AdaptiveConsts C;
-  std::memset((void*)&C, 0, sizeof C);  // the block is compared byte-wise with the cached copy below
-  C.r.rtol = rtol; C.r.t0 = t0; C.r.h0 = h0; C.r.n_eval = (int)n_eval; C.r.member_lanes = 0;
-  C.r.ls_steptol = std::pow(2.220446049250313e-16, 2.0 / 3.0);
-  if (opts) C.r.o = *opts; else dsh_adaptive_default_options(&C.r.o);
-  if (C.r.o.max_steps <= 0) C.r.o.max_steps = 10000000;
-  DSH_REQUIRE(C.r.o.group == 1 || C.r.o.group == 64, "adaptive group must be 1 (per member) or 64 (wavefront lock-step)");
+  std::memset((void*)&C, 0, sizeof C);  // the block is compared byte-wise with the cached copy (ResidentLaunch::open)
+  fill_resident(C.r, a);
+  DSH_REQUIRE_AS(who, C.r.o.group == 1 || C.r.o.group == 64, "adaptive group must be 1 (per member) or 64 (wavefront lock-step)");
   {
     // per-member control of the register-resident kernel: DSH_MEMBER_LANES = 32 | 16 | 8 puts that many members on a wavefront (profiles/r05_member_lanes.md); 0 / unset: 64
     static const int member_lanes_env = [] { const char* e = std::getenv("DSH_MEMBER_LANES"); const int v = e && *e ? std::atoi(e) : 0; return (v == 8 || v == 16 || v == 32) ? v : 0; }();
-    C.r.member_lanes = (C.r.o.group == 1 && !is_jit_model(model) && !sens && !steps) ? member_lanes_env : 0;
+    C.r.member_lanes = (C.r.o.group == 1 && !is_jit_model(model) && !sens && !a.steps) ? member_lanes_env : 0;
   }
-  if (steps) { C.steps_t_out = steps->t_out; C.steps_cap = (int)steps->cap; }
+  fill_steps(C, a.steps);
   C.simds = 4 * ctx->num_cu;  // the lock-step fast kernel's priority policy runs in launches with more wavefronts than this (DSH_PAIR_PRIO, dsh_adaptive_kernel.hpp)
 #if DSH_WAVE_TIMELINE
   C.timeline = wave_timeline_buffer((nb + 63) / 64);
 #endif
-  if (sens) {
-    C.sens_out = sens->out; C.sens_rtol = sens->rtol; C.sens_error_control = sens->natol > 0 ? 1 : 0;
-    int64_t ns = 0, npar_ = 0, nroots_ = 0; int hm_ = 0;
-    if (dsh_model_info(model, size, &ns, &npar_, &hm_, &nroots_) != DSH_OK) return DSH_E_INVALID;
-    DSH_REQUIRE(sens->natol == 0 || sens->natol == 1 || sens->natol == ns, "sens_atol must have length 1 or nstates");
-    bool uniform = true;
-    for (int64_t i = 1; i < sens->natol; ++i) uniform = uniform && sens->atol_host[i] == sens->atol_host[0];
-    DSH_REQUIRE(ns <= 4 || uniform, "device-resident sensitivities of models with more than 4 states take one sens_atol for every state");
-    C.sens_pad = (ns > 4 || sens->natol <= 1) ? 1 : 0;  // 1: sens_atol[0] for every state
-    for (int64_t i = 0; i < 4 && i < ns; ++i) C.sens_atol[i] = sens->natol == 0 ? 0.0 : (sens->natol == 1 ? sens->atol_host[0] : sens->atol_host[i]);
-  }
-  {  // Bdf::_new tables (bdf.rs:286-306)
-    // the one function the per-order bodies of the lock-step fast kernel evaluate at compile time (dsh_bdf_tables.hpp): the same 64-bit patterns
-    const BdfTables T = bdf_new_tables();
-    for (int i = 0; i <= kMaxOrder; ++i) { C.alpha[i] = T.alpha[i]; C.gamma[i] = T.gamma[i]; C.ec2[i] = T.ec2[i]; }
-    C.r.eta_reset = std::pow(20.0, 1.25);
-    C.r.eta_reset_ts = std::pow(100.0, 1.25);
-    C.eta_reset_p08 = dsh_det_pow(C.r.eta_reset, 0.8);  // used by the kernel only with the deterministic pow (the same function there)
-    C.eta_reset_ts_p08 = dsh_det_pow(C.r.eta_reset_ts, 0.8);
-    for (int ord = 1; ord <= kMaxOrder; ++ord) {  // compute_r(order, 1.0) (bdf.rs:433-463), stored 6x6 column-major
-      double* U = C.u[ord - 1];
-      for (int k = 0; k < 36; ++k) U[k] = 0.0;
-      for (int j = 0; j <= ord; ++j) U[j * 6 + 0] = 1.0;
-      for (int j = 1; j <= ord; ++j)
-        for (int i = 1; i <= ord; ++i) U[j * 6 + i] = U[j * 6 + i - 1] * ((double)i - 1.0 - 1.0 * (double)j) / (double)i;
-    }
-  }
-  double* t_eval_dev = nullptr;
-  unsigned long long* totals_dev = nullptr;
-  AdaptiveConsts* consts_dev = nullptr;
-  int rc = DSH_OK;
-  // Repeated solves of one problem (a parameter study, the benchmark loop) pass the same constants and save points every time: they stay on the device
-  // and are compared on the host instead of being uploaded again (two pageable host-to-device copies, ~15 us each on a 2.5 ms solve).  One small block per
-  // context, released with it.
-  const size_t cbytes = sizeof(AdaptiveConsts), tbytes = sizeof(double) * (size_t)n_eval, need = cbytes + tbytes;
-  bool cached = false;
-  if (tbytes <= 4096) {  // the block belongs to the context (one thread per context) and goes with it (dsh_ctx_destroy)
-    if (!ctx->const_cache_dev && hipMalloc((void**)&ctx->const_cache_dev, cbytes + 4096) != hipSuccess) { (void)hipGetLastError(); ctx->const_cache_dev = nullptr; }
-    if (ctx->const_cache_dev) {
-      if (!ctx->const_cache_host) ctx->const_cache_host = new std::vector<unsigned char>();
-      std::vector<unsigned char>& held = *ctx->const_cache_host;
-      std::vector<unsigned char> now(need);
-      std::memcpy(now.data(), &C, cbytes);
-      std::memcpy(now.data() + cbytes, t_eval_host, tbytes);
-      if (now != held) {
-        held.swap(now);  // the staging vector must outlive the asynchronous copy: it is the cache itself
-        DSH_HIP_CHECK(hipMemcpyAsync(ctx->const_cache_dev, held.data(), need, hipMemcpyHostToDevice, ctx->stream));
-        DSH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      }
-      consts_dev = (AdaptiveConsts*)ctx->const_cache_dev;
-      t_eval_dev = (double*)(ctx->const_cache_dev + cbytes);
-      cached = true;
-    }
-  }
-  if (!cached) {
-    rc = dsh_malloc(ctx, (int64_t)sizeof(AdaptiveConsts), 0, (void**)&consts_dev);
-    if (rc != DSH_OK) return rc;
-    DSH_HIP_CHECK(hipMemcpyAsync(consts_dev, &C, sizeof(AdaptiveConsts), hipMemcpyHostToDevice, ctx->stream));
-    rc = dsh_malloc(ctx, (int64_t)(sizeof(double) * n_eval), 0, (void**)&t_eval_dev);
-    if (rc != DSH_OK) return rc;
-    DSH_HIP_CHECK(hipMemcpyAsync(t_eval_dev, t_eval_host, sizeof(double) * n_eval, hipMemcpyHostToDevice, ctx->stream));
-  }
-  rc = dsh_malloc(ctx, (int64_t)(sizeof(unsigned long long) * 8), 1, (void**)&totals_dev);
-  if (rc != DSH_OK) { if (!cached) { dsh_free(ctx, t_eval_dev); dsh_free(ctx, consts_dev); } return rc; }
-  const bool ba = atol_nb == 1 && nb != 1;
+  if (const int rc = fill_sens(C, a.sens, model, size, true, who); rc != DSH_OK) return rc;
+  fill_bdf_tables(C.alpha, C.gamma, C.ec2, C.u);
+  C.eta_reset_p08 = dsh_det_pow(C.r.eta_reset, 0.8);  // used by the kernel only with the deterministic pow (the same function there)
+  C.eta_reset_ts_p08 = dsh_det_pow(C.r.eta_reset_ts, 0.8);
+  const bool ba = a.atol_nb == 1 && nb != 1;
+  const bool wave = C.r.o.group == 64;
   const int per_wave = C.r.member_lanes > 0 ? C.r.member_lanes : 64;
   const dim3 grid((unsigned)((nb + per_wave - 1) / per_wave)), blk(64);
-  bool launched = false;
-  DSH_HIP_CHECK(timing_begin(ctx));
+  ResidentLaunch L(ctx);
+  if (const int rc = L.open(&C, sizeof C, a.t_eval_host, a.n_eval, true); rc != DSH_OK) return rc;
+  const AdaptiveConsts* const consts_dev = (const AdaptiveConsts*)L.consts;
+  const double* const t_eval_dev = L.t_eval;
+  unsigned long long* const totals_dev = L.totals;
 #ifdef DSH_EXPERIMENTS
   // ---- per-member control in SEGMENTS with re-binning between them (DSH_REBIN=k: a segment ends when a member has produced k more save points; 0 / unset:
   // one launch).  Members drift apart inside a wavefront — different orders, step sizes, distances to the next order selection — and a wavefront pays for the
@@ -311,7 +246,8 @@ int bdf_solve_adaptive_impl(dsh_ctx* ctx, int model, int64_t size, int64_t nb, c
   // DSH_REBIN_STEPS=k: a segment ends for a member after k trips of its step loop instead (all wavefronts of a segment then do the same number of trips: no
   // waiting for the slowest member of a segment); the host launches segments until no member is left, then one launch that only writes the results.
   const int rebin_steps = [] { const char* e = std::getenv("DSH_REBIN_STEPS"); return e && *e ? std::atoi(e) : 0; }();
-  if (!sens && !steps && (rebin_steps > 0 || (rebin > 0 && n_eval > rebin)) && !is_jit_model(model) && C.r.o.group == 1 && nb >= 128) {
+  const int64_t n_eval = a.n_eval;
+  if (!sens && !a.steps && (rebin_steps > 0 || (rebin > 0 && n_eval > rebin)) && !is_jit_model(model) && C.r.o.group == 1 && nb >= 128) {
     double* seg_dbl = nullptr; int* seg_int = nullptr; unsigned long long *keys = nullptr, *keys_out = nullptr; int *idx_iota = nullptr, *lane_member = nullptr; void* cub_tmp = nullptr;
     AdaptiveConsts* seg_consts = nullptr; unsigned int* remaining = nullptr;
     size_t cub_bytes = 0;
@@ -323,7 +259,7 @@ int bdf_solve_adaptive_impl(dsh_ctx* ctx, int model, int64_t size, int64_t nb, c
                hipMalloc((void**)&keys, 8 * (size_t)nb) == hipSuccess && hipMalloc((void**)&keys_out, 8 * (size_t)nb) == hipSuccess && hipMalloc((void**)&idx_iota, 4 * (size_t)nb) == hipSuccess &&
                hipMalloc((void**)&lane_member, 4 * (size_t)nb) == hipSuccess && hipMalloc(&cub_tmp, cub_bytes ? cub_bytes : 8) == hipSuccess &&
                hipMalloc((void**)&seg_consts, sizeof(AdaptiveConsts) * (size_t)nseg) == hipSuccess && hipMalloc((void**)&remaining, 4) == hipSuccess;
-    if (!okm) { (void)hipGetLastError(); release(); set_error("dsh_bdf_solve_adaptive (DSH_REBIN): out of device memory for the segment state"); dsh_free(ctx, totals_dev); if (!cached) { dsh_free(ctx, t_eval_dev); dsh_free(ctx, consts_dev); } return DSH_E_HIP; }
+    if (!okm) { (void)hipGetLastError(); release(); set_error("dsh_bdf_solve_adaptive (DSH_REBIN): out of device memory for the segment state"); return DSH_E_HIP; }
     {
       std::vector<int> iota((size_t)nb);
       for (int64_t k = 0; k < nb; ++k) iota[(size_t)k] = (int)k;
@@ -367,17 +303,9 @@ int bdf_solve_adaptive_impl(dsh_ctx* ctx, int model, int64_t size, int64_t nb, c
           (void)hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_bytes, keys, keys_out, idx_iota, lane_member, (int)nb, 0, 64, ctx->stream);
       }
     }
-    DSH_HIP_CHECK(hipGetLastError());
-    DSH_HIP_CHECK(timing_end(ctx));
-    unsigned long long totals_s[8] = {0};
-    DSH_HIP_CHECK(hipMemcpyAsync(totals_s, totals_dev, sizeof(unsigned long long) * 6, hipMemcpyDeviceToHost, ctx->stream));
-    DSH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    DSH_HIP_CHECK(timing_collect(ctx));
+    const int rc = L.close(a.totals_host);
     release();
-    if (!cached) { dsh_free(ctx, t_eval_dev); dsh_free(ctx, consts_dev); }
-    dsh_free(ctx, totals_dev);
-    if (totals_host) for (int k = 0; k < 6; ++k) totals_host[k] = (int64_t)totals_s[k];
-    return DSH_OK;
+    return rc;
   }
 #endif  // DSH_EXPERIMENTS
   // per-member control of the register-resident models can run on the phase-scheduled kernel (dsh_member_sched_kernel.hpp; same bits) with
@@ -400,55 +328,40 @@ int bdf_solve_adaptive_impl(dsh_ctx* ctx, int model, int64_t size, int64_t nb, c
     // config 4 is 2) the small-ensemble build (dsh_jit.hip compile_module: one wavefront per SIMD, deeper unrolling, doubled chunks); DSH_LANE_BANDED_SMALL=0 / 1 forces
     static const int small_env = [] { const char* e = std::getenv("DSH_LANE_BANDED_SMALL"); return e && *e ? std::atoi(e) : -1; }();
     const bool small = lane_v2 && !sched && (small_env >= 0 ? small_env != 0 : nb < (int64_t)4 * 64 * ctx->num_cu);
-    rc = jit_launch(ctx, model, sched ? "dsh_member_sched_kernel.hpp" : (lane_v2 ? "dsh_lane_banded_kernel.hpp" : "dsh_adaptive_kernel.hpp"), small ? name + "#small" : name, {name}, name, grid, blk, 0, nb, p, atol, (const AdaptiveConsts*)consts_dev, (const double*)t_eval_dev, y_out,
-                    stats, status, t_root, root_idx, ncols, totals_dev);
-    if (rc != DSH_OK) { if (!cached) { dsh_free(ctx, t_eval_dev); dsh_free(ctx, consts_dev); } dsh_free(ctx, totals_dev); return rc; }
-    launched = true;
+    const int rc = jit_launch(ctx, model, sched ? "dsh_member_sched_kernel.hpp" : (lane_v2 ? "dsh_lane_banded_kernel.hpp" : "dsh_adaptive_kernel.hpp"), small ? name + "#small" : name, {name},
+                              name, grid, blk, 0, nb, p, atol, consts_dev, t_eval_dev, y_out, stats, status, t_root, root_idx, ncols, totals_dev);
+    if (rc != DSH_OK) return rc;
   } else
   if (!sens && C.r.o.deterministic_pow == 2 &&
       // the fast-arithmetic variant (dsh_adaptive_fast.hip): static models with n <= 4; everything else about the call is the same.  A model without that build
       // falls through to the exact kernel below (its `det` is "deterministic_pow != 0")
-      adaptive_fast_launch(model, size, ba, C.r.o.group == 64, C.r.o, grid, ctx->stream, nb, p, atol, (const AdaptiveConsts*)consts_dev, (const double*)t_eval_dev, y_out, stats,
-                           status, t_root, root_idx, ncols, totals_dev)) {
-    launched = true;
+      adaptive_fast_launch(model, size, ba, wave, C.r.o, grid, ctx->stream, nb, p, atol, consts_dev, t_eval_dev, y_out, stats, status, t_root, root_idx, ncols, totals_dev)) {
   } else if (sens) {
-    launched = dispatch_static_model(model, size, [&](auto mdl) {
+    dispatch_static_model(model, size, [&](auto mdl) {
       using Mdl = decltype(mdl);
-      if constexpr (adaptive_sens_ok<Mdl>()) {
-#define DSH_ADAPTIVE_SENS_LAUNCH(BA, WAVE) \
-  hipLaunchKernelGGL((k_bdf_adaptive<Mdl, BA, WAVE, false, true>), grid, blk, 0, ctx->stream, nb, p, atol, (const AdaptiveConsts*)consts_dev, (const double*)t_eval_dev, y_out, stats, status, t_root, root_idx, ncols, totals_dev)
-        if (C.r.o.group == 64) { if (ba) DSH_ADAPTIVE_SENS_LAUNCH(true, true); else DSH_ADAPTIVE_SENS_LAUNCH(false, true); }
-        else { if (ba) DSH_ADAPTIVE_SENS_LAUNCH(true, false); else DSH_ADAPTIVE_SENS_LAUNCH(false, false); }
-#undef DSH_ADAPTIVE_SENS_LAUNCH
-      }
+      if constexpr (adaptive_sens_ok<Mdl>())
+        with_bools(ba, wave, [&](auto BA, auto WAVE) {
+          hipLaunchKernelGGL((k_bdf_adaptive<Mdl, decltype(BA)::value, decltype(WAVE)::value, false, true>), grid, blk, 0, ctx->stream, nb, p, atol, consts_dev, t_eval_dev, y_out,
+                             stats, status, t_root, root_idx, ncols, totals_dev);
+        });
     });
   } else
-  launched = dispatch_static_model(model, size, [&](auto mdl) {
+  dispatch_static_model(model, size, [&](auto mdl) {
     using Mdl = decltype(mdl);
-    if constexpr (Mdl::N <= 4) {
-#define DSH_ADAPTIVE_LAUNCH(BA, WAVE) \
-  hipLaunchKernelGGL((k_bdf_adaptive<Mdl, BA, WAVE>), grid, blk, 0, ctx->stream, nb, p, atol, (const AdaptiveConsts*)consts_dev, (const double*)t_eval_dev, y_out, stats, status, t_root, root_idx, ncols, totals_dev)
-      if (C.r.o.group == 64) { if (ba) DSH_ADAPTIVE_LAUNCH(true, true); else DSH_ADAPTIVE_LAUNCH(false, true); }
+    if constexpr (Mdl::N <= 4)
+      with_bools(ba, wave, [&](auto BA, auto WAVE) {
 #ifdef DSH_EXPERIMENTS
-      else if (sched_env) {
-        if (ba) hipLaunchKernelGGL((k_bdf_member_sched<Mdl, true>), grid, blk, 0, ctx->stream, nb, p, atol, (const AdaptiveConsts*)consts_dev, (const double*)t_eval_dev, y_out, stats, status, t_root, root_idx, ncols, totals_dev);
-        else hipLaunchKernelGGL((k_bdf_member_sched<Mdl, false>), grid, blk, 0, ctx->stream, nb, p, atol, (const AdaptiveConsts*)consts_dev, (const double*)t_eval_dev, y_out, stats, status, t_root, root_idx, ncols, totals_dev);
-      }
+        if constexpr (!decltype(WAVE)::value)
+          if (sched_env) {
+            hipLaunchKernelGGL((k_bdf_member_sched<Mdl, decltype(BA)::value>), grid, blk, 0, ctx->stream, nb, p, atol, consts_dev, t_eval_dev, y_out, stats, status, t_root, root_idx,
+                               ncols, totals_dev);
+            return;
+          }
 #endif
-      else { if (ba) DSH_ADAPTIVE_LAUNCH(true, false); else DSH_ADAPTIVE_LAUNCH(false, false); }
-#undef DSH_ADAPTIVE_LAUNCH
-    }
+        hipLaunchKernelGGL((k_bdf_adaptive<Mdl, decltype(BA)::value, decltype(WAVE)::value>), grid, blk, 0, ctx->stream, nb, p, atol, consts_dev, t_eval_dev, y_out, stats, status,
+                           t_root, root_idx, ncols, totals_dev);
+      });
   });
-  (void)launched;
-  DSH_HIP_CHECK(hipGetLastError());
-  DSH_HIP_CHECK(timing_end(ctx));
-  unsigned long long totals[8] = {0};
-  DSH_HIP_CHECK(hipMemcpyAsync(totals, totals_dev, sizeof(unsigned long long) * 6, hipMemcpyDeviceToHost, ctx->stream));
-  DSH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  DSH_HIP_CHECK(timing_collect(ctx));
-  if (!cached) { dsh_free(ctx, t_eval_dev); dsh_free(ctx, consts_dev); }
-  dsh_free(ctx, totals_dev);
-  if (totals_host) for (int k = 0; k < 6; ++k) totals_host[k] = (int64_t)totals[k];
-  return DSH_OK;
+  return L.close(a.totals_host);
 }
 }  // namespace

@@ -13,8 +13,7 @@
 #include <cstring>
 #include <string>
 
-#include "dsh_internal.hpp"
-#include "dsh_resident.hpp"
+#include "dsh_resident_host.hpp"
 
 #include "dsh_erk_kernel.hpp"
 #include "dsh_jit.hpp"
@@ -57,9 +56,6 @@ int erk_model_has_sens(int model, int64_t size) {
 }  // namespace dsh
 
 namespace {
-struct ErkStepsSpec { double* t_out; int64_t cap; };
-struct ErkSensSpec { double* out; double rtol; const double* atol_host; int64_t natol; };
-
 // why a model is refused, in the caller's words
 int erk_refuse(int model, int64_t size) {
   int64_t n = 0, np = 0, nroots = 0;
@@ -85,90 +81,55 @@ int erk_refuse_sens(int model, int64_t size) {
   return DSH_E_UNSUPPORTED;
 }
 
-int erk_solve_resident_impl(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol, double t0,
-                            double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double* y_out, int32_t* stats, int32_t* status,
-                            double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host, const ErkStepsSpec* steps, const ErkSensSpec* sens = nullptr) {
-  DSH_REQUIRE(ctx != nullptr, "ctx is null");
-  DSH_REQUIRE(method == 3, "method must be 3 (Tsit45)");
-  DSH_REQUIRE(n_eval >= 1 && t_eval_host != nullptr, "t_eval must hold at least one time");
-  DSH_REQUIRE(atol_nb == 1 || atol_nb == nb, "atol must be broadcast (nbatch 1) or per member");
-  for (int64_t q = 0; q + 1 < n_eval; ++q) DSH_REQUIRE(t_eval_host[q] <= t_eval_host[q + 1], "t_eval must be increasing (InvalidTEval)");
-  DSH_REQUIRE(t_eval_host[0] >= t0, "t_eval[0] before t0 (InvalidTEval)");
+int erk_solve_resident_impl(const SolveArgs& a, int method) {
+  static const char* const who = "dsh_erk_solve_resident";
+  DSH_REQUIRE_AS(who, method == 3, "method must be 3 (Tsit45)");
+  if (const int rc = check_solve_args(a, who); rc != DSH_OK) return rc;
+  dsh_ctx* const ctx = a.ctx;
+  const int model = a.model;
+  const int64_t size = a.size, nb = a.nb;
+  const bool sens = a.sens != nullptr;
   if (!erk_model_has_resident(model, size)) return erk_refuse(model, size);
   if (sens && !erk_model_has_sens(model, size)) return erk_refuse_sens(model, size);
   if (nb == 0) return DSH_OK;
   ErkConsts T;
   std::memset((void*)&T, 0, sizeof T);
-  T.r.rtol = rtol; T.r.t0 = t0; T.r.h0 = h0; T.r.n_eval = (int)n_eval; T.r.member_lanes = 0;
-  if (opts) T.r.o = *opts; else dsh_adaptive_default_options(&T.r.o);
-  if (T.r.o.max_steps <= 0) T.r.o.max_steps = 10000000;
-  DSH_REQUIRE(T.r.o.group == 1 || T.r.o.group == 64, "group must be 1 (per member) or 64 (wavefront lock-step)");
+  fill_resident(T.r, a);
+  DSH_REQUIRE_AS(who, T.r.o.group == 1 || T.r.o.group == 64, "group must be 1 (per member) or 64 (wavefront lock-step)");
   // ExplicitRkConfig::default() (config.rs:141-160): NOT the BDF / SDIRK bounds dsh_adaptive_options carries
   T.min_shrink = 0.5; T.max_shrink = 1.0; T.min_growth = 1.0; T.max_growth = 2.0;
-  if (steps) { T.steps_t_out = steps->t_out; T.steps_cap = (int)steps->cap; }
-  if (sens) {  // as dsh_sdirk_solve_resident_sens (admitted models have at most 4 states)
-    T.sens_out = sens->out; T.sens_rtol = sens->rtol; T.sens_error_control = sens->natol > 0 ? 1 : 0;
-    int64_t ns = 0, npar_ = 0, nroots_ = 0; int hm_ = 0;
-    if (dsh_model_info(model, size, &ns, &npar_, &hm_, &nroots_) != DSH_OK) return DSH_E_INVALID;
-    DSH_REQUIRE(sens->natol == 0 || sens->natol == 1 || sens->natol == ns, "sens_atol must have length 1 or nstates");
-    T.sens_pad = sens->natol <= 1 ? 1 : 0;  // 1: sens_atol[0] for every state
-    for (int64_t i = 0; i < 4 && i < ns; ++i) T.sens_atol[i] = sens->natol == 0 ? 0.0 : (sens->natol == 1 ? sens->atol_host[0] : sens->atol_host[i]);
-  }
-  double* t_eval_dev = nullptr;
-  unsigned long long* totals_dev = nullptr;
-  ErkConsts* consts_dev = nullptr;
-  int rc = dsh_malloc(ctx, (int64_t)sizeof(ErkConsts), 0, (void**)&consts_dev);
-  if (rc != DSH_OK) return rc;
-  DSH_HIP_CHECK(hipMemcpyAsync(consts_dev, &T, sizeof(ErkConsts), hipMemcpyHostToDevice, ctx->stream));
-  rc = dsh_malloc(ctx, (int64_t)(sizeof(double) * n_eval), 0, (void**)&t_eval_dev);
-  if (rc != DSH_OK) return rc;
-  rc = dsh_malloc(ctx, (int64_t)(sizeof(unsigned long long) * 8), 1, (void**)&totals_dev);
-  if (rc != DSH_OK) return rc;
-  DSH_HIP_CHECK(hipMemcpyAsync(t_eval_dev, t_eval_host, sizeof(double) * n_eval, hipMemcpyHostToDevice, ctx->stream));
-  const bool ba = atol_nb == 1 && nb != 1;
+  fill_steps(T, a.steps);
+  if (const int rc = fill_sens(T, a.sens, model, size, false, who); rc != DSH_OK) return rc;  // admitted models with parameters have at most 4 states
+  const bool ba = a.atol_nb == 1 && nb != 1;
   const bool wave = T.r.o.group == 64;
   const dim3 grid((unsigned)((nb + 63) / 64)), blk(64);  // 64 members per wavefront in both modes
-  DSH_HIP_CHECK(timing_begin(ctx));
+  ResidentLaunch L(ctx);
+  if (const int rc = L.open(&T, sizeof T, a.t_eval_host, a.n_eval); rc != DSH_OK) return rc;
+  const ErkConsts* const consts_dev = (const ErkConsts*)L.consts;
   if (is_jit_model(model)) {
     const std::string name = std::string("dsh::k_erk_resident<dsh::JitModel, ") + (ba ? "true" : "false") + ", " + (wave ? "true" : "false") + (sens ? ", true>" : ">");
-    rc = jit_launch(ctx, model, "dsh_erk_kernel.hpp", name, {name}, name, grid, blk, 0, nb, p, atol, (const ErkConsts*)consts_dev, (const double*)t_eval_dev, y_out, stats,
-                    status, t_root, root_idx, ncols, totals_dev);
+    const int rc = jit_launch(ctx, model, "dsh_erk_kernel.hpp", name, {name}, name, grid, blk, 0, nb, a.p, a.atol, consts_dev, L.t_eval, a.y_out, a.stats, a.status, a.t_root,
+                              a.root_idx, a.ncols, L.totals);
     if (rc != DSH_OK) return rc;
   } else if (sens) {
     dispatch_static_model(model, size, [&](auto mdl) {
       using Mdl = decltype(mdl);
-      if constexpr (erk_sens_ok<Mdl>()) {
-#define DSH_ERK_SENS_LAUNCH(BA, WAVE)                                                                                                                         \
-  hipLaunchKernelGGL((k_erk_resident<Mdl, BA, WAVE, true>), grid, blk, 0, ctx->stream, nb, p, atol, (const ErkConsts*)consts_dev, (const double*)t_eval_dev, \
-                     y_out, stats, status, t_root, root_idx, ncols, totals_dev)
-        if (ba) { if (wave) DSH_ERK_SENS_LAUNCH(true, true); else DSH_ERK_SENS_LAUNCH(true, false); }
-        else { if (wave) DSH_ERK_SENS_LAUNCH(false, true); else DSH_ERK_SENS_LAUNCH(false, false); }
-#undef DSH_ERK_SENS_LAUNCH
-      }
+      if constexpr (erk_sens_ok<Mdl>())
+        with_bools(ba, wave, [&](auto BA, auto WAVE) {
+          hipLaunchKernelGGL((k_erk_resident<Mdl, decltype(BA)::value, decltype(WAVE)::value, true>), grid, blk, 0, ctx->stream, nb, a.p, a.atol, consts_dev, L.t_eval,
+                             a.y_out, a.stats, a.status, a.t_root, a.root_idx, a.ncols, L.totals);
+        });
     });
   } else
   dispatch_static_model(model, size, [&](auto mdl) {
     using Mdl = decltype(mdl);
-    if constexpr (Mdl::N <= 4 && !Mdl::HAS_MASS && !model_has_reset<Mdl>::value) {
-#define DSH_ERK_LAUNCH(BA, WAVE)                                                                                                                        \
-  hipLaunchKernelGGL((k_erk_resident<Mdl, BA, WAVE>), grid, blk, 0, ctx->stream, nb, p, atol, (const ErkConsts*)consts_dev, (const double*)t_eval_dev, \
-                     y_out, stats, status, t_root, root_idx, ncols, totals_dev)
-      if (ba) { if (wave) DSH_ERK_LAUNCH(true, true); else DSH_ERK_LAUNCH(true, false); }
-      else { if (wave) DSH_ERK_LAUNCH(false, true); else DSH_ERK_LAUNCH(false, false); }
-#undef DSH_ERK_LAUNCH
-    }
+    if constexpr (Mdl::N <= 4 && !Mdl::HAS_MASS && !model_has_reset<Mdl>::value)
+      with_bools(ba, wave, [&](auto BA, auto WAVE) {
+        hipLaunchKernelGGL((k_erk_resident<Mdl, decltype(BA)::value, decltype(WAVE)::value>), grid, blk, 0, ctx->stream, nb, a.p, a.atol, consts_dev, L.t_eval, a.y_out,
+                           a.stats, a.status, a.t_root, a.root_idx, a.ncols, L.totals);
+      });
   });
-  DSH_HIP_CHECK(hipGetLastError());
-  DSH_HIP_CHECK(timing_end(ctx));
-  unsigned long long totals[8] = {0};
-  DSH_HIP_CHECK(hipMemcpyAsync(totals, totals_dev, sizeof(unsigned long long) * 6, hipMemcpyDeviceToHost, ctx->stream));
-  DSH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  DSH_HIP_CHECK(timing_collect(ctx));
-  dsh_free(ctx, t_eval_dev);
-  dsh_free(ctx, totals_dev);
-  dsh_free(ctx, consts_dev);
-  if (totals_host) for (int q = 0; q < 6; ++q) totals_host[q] = (int64_t)totals[q];
-  return DSH_OK;
+  return L.close(a.totals_host);
 }
 }  // namespace
 
@@ -178,8 +139,8 @@ int dsh_erk_solve_resident(dsh_ctx* ctx, int method, int model, int64_t size, in
                            double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double* y_out, int32_t* stats, int32_t* status,
                            double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host) {
   DSH_ENTER(ctx);
-  return erk_solve_resident_impl(ctx, method, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, t_eval_host, n_eval, y_out, stats, status, t_root, root_idx, ncols,
-                                 totals_host, nullptr);
+  return erk_solve_resident_impl({ctx, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, t_eval_host, n_eval, y_out, stats, status, t_root, root_idx, ncols, totals_host,
+                                  nullptr, nullptr}, method);
 }
 // 1 when dsh_erk_solve_resident_sens takes the model: see erk_model_has_sens above
 int dsh_erk_model_has_sens(int model, int64_t size) { return erk_model_has_sens(model, size); }
@@ -191,9 +152,9 @@ int dsh_erk_solve_resident_sens(dsh_ctx* ctx, int method, int model, int64_t siz
   DSH_ENTER(ctx);
   DSH_REQUIRE(sens_out != nullptr, "sens_out is null");
   DSH_REQUIRE(nsens_atol == 0 || sens_atol_host != nullptr, "sens_atol is null");
-  const ErkSensSpec sp{sens_out, sens_rtol, sens_atol_host, nsens_atol};
-  return erk_solve_resident_impl(ctx, method, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, t_eval_host, n_eval, y_out, stats, status, nullptr, nullptr, nullptr,
-                                 totals_host, nullptr, &sp);
+  const SensSpec sp{sens_out, sens_rtol, sens_atol_host, nsens_atol};
+  return erk_solve_resident_impl({ctx, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, t_eval_host, n_eval, y_out, stats, status, nullptr, nullptr, nullptr, totals_host,
+                                  &sp, nullptr}, method);
 }
 // OdeSolverMethod::solve (method.rs:227-258 over :881-961) inside the launch: the state after every accepted step of every member (arguments as
 // dsh_sdirk_solve_resident_steps)
@@ -202,8 +163,9 @@ int dsh_erk_solve_resident_steps(dsh_ctx* ctx, int method, int model, int64_t si
                                  int32_t* status, double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host) {
   DSH_ENTER(ctx);
   DSH_REQUIRE(max_cols >= 2 && max_cols <= 0x7fffffff && y_out != nullptr && t_out != nullptr && ncols != nullptr, "dsh_erk_solve_resident_steps: max_cols >= 2, y_out, t_out and ncols are needed");
-  const ErkStepsSpec st{t_out, max_cols};
-  return erk_solve_resident_impl(ctx, method, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, &t_final, 1, y_out, stats, status, t_root, root_idx, ncols, totals_host, &st);
+  const StepsSpec st{t_out, max_cols};
+  return erk_solve_resident_impl({ctx, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, &t_final, 1, y_out, stats, status, t_root, root_idx, ncols, totals_host, nullptr, &st},
+                                 method);
 }
 
 }  // extern "C"

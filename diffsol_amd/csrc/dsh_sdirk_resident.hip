@@ -14,8 +14,7 @@
 #include <cstring>
 #include <vector>
 
-#include "dsh_internal.hpp"
-#include "dsh_resident.hpp"
+#include "dsh_resident_host.hpp"
 
 #include "dsh_sdirk_kernel.hpp"
 #include "dsh_jit.hpp"
@@ -51,24 +50,19 @@ int dsh_model_has_resident(int method, int model, int64_t size) {
 
 }  // extern "C"
 namespace {
-struct SdirkSensSpec { double* out; double rtol; const double* atol_host; int64_t natol; };
-struct SdirkStepsSpec { double* t_out; int64_t cap; };  // OdeSolverMethod::solve: every accepted step out (SdirkConsts::steps_cap)
 template <class Mdl> constexpr bool sdirk_sens_ok() {
   if constexpr (model_has_sens<Mdl>::value) return Mdl::N <= 4 && !Mdl::HAS_MASS && Mdl::NROOTS == 0 && model_band_k<Mdl>::value == 0;
   else return false;
 }
-int sdirk_solve_resident_impl(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol,
-                              double t0, double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double* y_out, int32_t* stats,
-                              int32_t* status, double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host, const SdirkSensSpec* sens,
-                              const SdirkStepsSpec* steps = nullptr);
+int sdirk_solve_resident_impl(const SolveArgs& a, int method);
 }  // namespace
 extern "C" {
 int dsh_sdirk_solve_resident(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol,
                              double t0, double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double* y_out, int32_t* stats,
                              int32_t* status, double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host) {
   DSH_ENTER(ctx);
-  return sdirk_solve_resident_impl(ctx, method, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, t_eval_host, n_eval, y_out, stats, status, t_root, root_idx, ncols,
-                                   totals_host, nullptr);
+  return sdirk_solve_resident_impl({ctx, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, t_eval_host, n_eval, y_out, stats, status, t_root, root_idx, ncols, totals_host,
+                                    nullptr, nullptr}, method);
 }
 // OdeSolverMethod::solve (method.rs:227-258 over :881-961) inside the launch of the device-resident TR-BDF2 / ESDIRK34: the state after every accepted step of every member
 // (arguments as dsh_bdf_solve_adaptive_steps; the models of dsh_model_has_resident(method, ..))
@@ -77,8 +71,9 @@ int dsh_sdirk_solve_resident_steps(dsh_ctx* ctx, int method, int model, int64_t 
                                    int32_t* status, double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host) {
   DSH_ENTER(ctx);
   DSH_REQUIRE(max_cols >= 2 && max_cols <= 0x7fffffff && y_out != nullptr && t_out != nullptr && ncols != nullptr, "dsh_sdirk_solve_resident_steps: max_cols >= 2, y_out, t_out and ncols are needed");
-  const SdirkStepsSpec st{t_out, max_cols};
-  return sdirk_solve_resident_impl(ctx, method, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, &t_final, 1, y_out, stats, status, t_root, root_idx, ncols, totals_host, nullptr, &st);
+  const StepsSpec st{t_out, max_cols};
+  return sdirk_solve_resident_impl({ctx, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, &t_final, 1, y_out, stats, status, t_root, root_idx, ncols, totals_host, nullptr, &st},
+                                   method);
 }
 // TR-BDF2 / ESDIRK34 with forward sensitivities in the same launch (dsh_bdf_solve_adaptive_sens is the BDF): the same models (dsh_model_has_adaptive_sens)
 int dsh_sdirk_solve_resident_sens(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol,
@@ -91,30 +86,26 @@ int dsh_sdirk_solve_resident_sens(dsh_ctx* ctx, int method, int model, int64_t s
     set_error("dsh_sdirk_solve_resident_sens: the model has no device-resident integrator with forward sensitivities (identity-mass ODE model with parameter derivatives and no root functions: register-resident n <= 4, or the banded lane-per-member form)");
     return DSH_E_UNSUPPORTED;
   }
-  const SdirkSensSpec sp{sens_out, sens_rtol, sens_atol_host, nsens_atol};
-  return sdirk_solve_resident_impl(ctx, method, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, t_eval_host, n_eval, y_out, stats, status, nullptr, nullptr, nullptr,
-                                   totals_host, &sp);
+  const SensSpec sp{sens_out, sens_rtol, sens_atol_host, nsens_atol};
+  return sdirk_solve_resident_impl({ctx, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, t_eval_host, n_eval, y_out, stats, status, nullptr, nullptr, nullptr, totals_host,
+                                    &sp, nullptr}, method);
 }
 }  // extern "C"
 namespace {
-int sdirk_solve_resident_impl(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol,
-                              double t0, double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double* y_out, int32_t* stats,
-                              int32_t* status, double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host, const SdirkSensSpec* sens,
-                              const SdirkStepsSpec* steps) {
-  DSH_REQUIRE(ctx != nullptr, "ctx is null");
-  DSH_REQUIRE(method == 1 || method == 2, "method must be 1 (TR-BDF2) or 2 (ESDIRK34)");
-  DSH_REQUIRE(n_eval >= 1 && t_eval_host != nullptr, "t_eval must hold at least one time");
-  DSH_REQUIRE(atol_nb == 1 || atol_nb == nb, "atol must be broadcast (nbatch 1) or per member");
-  for (int64_t q = 0; q + 1 < n_eval; ++q) DSH_REQUIRE(t_eval_host[q] <= t_eval_host[q + 1], "t_eval must be increasing (InvalidTEval)");
-  DSH_REQUIRE(t_eval_host[0] >= t0, "t_eval[0] before t0 (InvalidTEval)");
+int sdirk_solve_resident_impl(const SolveArgs& a, int method) {
+  static const char* const who = "dsh_sdirk_solve_resident";
+  DSH_REQUIRE_AS(who, method == 1 || method == 2, "method must be 1 (TR-BDF2) or 2 (ESDIRK34)");
+  if (const int rc = check_solve_args(a, who); rc != DSH_OK) return rc;
+  dsh_ctx* const ctx = a.ctx;
+  const int model = a.model;
+  const int64_t size = a.size, nb = a.nb;
+  const bool sens = a.sens != nullptr;
   if (!dsh_model_has_resident(method, model, size)) { set_error("dsh_sdirk_solve_resident: model has no device-resident kernel (needs a static model, n <= 4)"); return DSH_E_UNSUPPORTED; }
   if (nb == 0) return DSH_OK;
   SdirkConsts T;
   std::memset((void*)&T, 0, sizeof T);
-  T.r.rtol = rtol; T.r.t0 = t0; T.r.h0 = h0; T.r.n_eval = (int)n_eval; T.r.member_lanes = 0;
-  if (opts) T.r.o = *opts; else dsh_adaptive_default_options(&T.r.o);
-  if (T.r.o.max_steps <= 0) T.r.o.max_steps = 10000000;
-  DSH_REQUIRE(T.r.o.group == 1 || T.r.o.group == 64, "group must be 1 (per member) or 64 (wavefront lock-step)");
+  fill_resident(T.r, a);
+  DSH_REQUIRE_AS(who, T.r.o.group == 1 || T.r.o.group == 64, "group must be 1 (per member) or 64 (wavefront lock-step)");
   {
     // per-member control: DSH_MEMBER_LANES = 32 | 16 | 8 puts that many members on a wavefront (measured in profiles/r05_member_lanes.md); 0 / unset: 64
     static const int member_lanes_env = [] { const char* e = std::getenv("DSH_MEMBER_LANES"); const int v = e && *e ? std::atoi(e) : -1; return (v == 8 || v == 16 || v == 32 || v == 64) ? v : -1; }();
@@ -126,85 +117,43 @@ int sdirk_solve_resident_impl(dsh_ctx* ctx, int method, int model, int64_t size,
     const int auto_lanes = ((nb + 63) / 64 * 2 >= simds && (nb + 31) / 32 <= 2 * simds) ? 32 : 0;
     T.r.member_lanes = (T.r.o.group == 1 && !is_jit_model(model)) ? (member_lanes_env > 0 ? (member_lanes_env == 64 ? 0 : member_lanes_env) : auto_lanes) : 0;
   }
-  T.r.eta_reset = std::pow(20.0, 1.25);
-  T.r.eta_reset_ts = std::pow(100.0, 1.25);
-  T.r.ls_steptol = std::pow(2.220446049250313e-16, 2.0 / 3.0);
-  fill_tableau(method, T);
-  if (steps) { T.steps_t_out = steps->t_out; T.steps_cap = (int)steps->cap; }
-  if (sens) {
-    T.sens_out = sens->out; T.sens_rtol = sens->rtol; T.sens_error_control = sens->natol > 0 ? 1 : 0;
-    int64_t ns = 0, npar_ = 0, nroots_ = 0; int hm_ = 0;
-    if (dsh_model_info(model, size, &ns, &npar_, &hm_, &nroots_) != DSH_OK) return DSH_E_INVALID;
-    DSH_REQUIRE(sens->natol == 0 || sens->natol == 1 || sens->natol == ns, "sens_atol must have length 1 or nstates");
-    bool uniform = true;
-    for (int64_t i = 1; i < sens->natol; ++i) uniform = uniform && sens->atol_host[i] == sens->atol_host[0];
-    DSH_REQUIRE(ns <= 4 || uniform, "device-resident sensitivities of models with more than 4 states take one sens_atol for every state");
-    T.sens_pad = (ns > 4 || sens->natol <= 1) ? 1 : 0;  // 1: sens_atol[0] for every state
-    for (int64_t i = 0; i < 4 && i < ns; ++i) T.sens_atol[i] = sens->natol == 0 ? 0.0 : (sens->natol == 1 ? sens->atol_host[0] : sens->atol_host[i]);
-  }
-  double* t_eval_dev = nullptr;
-  unsigned long long* totals_dev = nullptr;
-  SdirkConsts* consts_dev = nullptr;
-  int rc = dsh_malloc(ctx, (int64_t)sizeof(SdirkConsts), 0, (void**)&consts_dev);
-  if (rc != DSH_OK) return rc;
-  DSH_HIP_CHECK(hipMemcpyAsync(consts_dev, &T, sizeof(SdirkConsts), hipMemcpyHostToDevice, ctx->stream));
-  rc = dsh_malloc(ctx, (int64_t)(sizeof(double) * n_eval), 0, (void**)&t_eval_dev);
-  if (rc != DSH_OK) return rc;
-  rc = dsh_malloc(ctx, (int64_t)(sizeof(unsigned long long) * 8), 1, (void**)&totals_dev);
-  if (rc != DSH_OK) return rc;
-  DSH_HIP_CHECK(hipMemcpyAsync(t_eval_dev, t_eval_host, sizeof(double) * n_eval, hipMemcpyHostToDevice, ctx->stream));
-  const bool ba = atol_nb == 1 && nb != 1;
+  fill_tableau(method, T);  // resets the steps fields: ahead of fill_steps
+  fill_steps(T, a.steps);
+  if (const int rc = fill_sens(T, a.sens, model, size, true, who); rc != DSH_OK) return rc;
+  const bool ba = a.atol_nb == 1 && nb != 1;
   const bool wave = T.r.o.group == 64;
   const int per_wave = T.r.member_lanes > 0 ? T.r.member_lanes : 64;
   const dim3 grid((unsigned)((nb + per_wave - 1) / per_wave)), blk(64);
-  DSH_HIP_CHECK(timing_begin(ctx));
+  ResidentLaunch L(ctx);
+  if (const int rc = L.open(&T, sizeof T, a.t_eval_host, a.n_eval); rc != DSH_OK) return rc;
+  const SdirkConsts* const consts_dev = (const SdirkConsts*)L.consts;
   if (is_jit_model(model)) {
     const std::string name = std::string("dsh::k_sdirk_resident<dsh::JitModel, ") + (ba ? "true" : "false") + ", " + (wave ? "true" : "false") + ", " + (method == 1 ? "3" : "4") + (sens ? ", true>" : ">");
-    rc = jit_launch(ctx, model, "dsh_sdirk_kernel.hpp", name, {name}, name, grid, blk, 0, nb, p, atol, (const SdirkConsts*)consts_dev, (const double*)t_eval_dev, y_out, stats,
-                    status, t_root, root_idx, ncols, totals_dev);
+    const int rc = jit_launch(ctx, model, "dsh_sdirk_kernel.hpp", name, {name}, name, grid, blk, 0, nb, a.p, a.atol, consts_dev, L.t_eval, a.y_out, a.stats, a.status, a.t_root,
+                              a.root_idx, a.ncols, L.totals);
     if (rc != DSH_OK) return rc;
   } else if (!sens && T.r.o.deterministic_pow == 2 &&
              // the fast-arithmetic build (dsh_sdirk_fast.hip): static models with n <= 4; a model without it falls through to the exact kernel below
-             sdirk_fast_launch(method, model, size, ba, wave, grid, ctx->stream, nb, p, atol, (const SdirkConsts*)consts_dev, (const double*)t_eval_dev, y_out, stats, status,
-                               t_root, root_idx, ncols, totals_dev)) {
+             sdirk_fast_launch(method, model, size, ba, wave, grid, ctx->stream, nb, a.p, a.atol, consts_dev, L.t_eval, a.y_out, a.stats, a.status, a.t_root, a.root_idx,
+                               a.ncols, L.totals)) {
   } else if (sens) {
     dispatch_static_model(model, size, [&](auto mdl) {
       using Mdl = decltype(mdl);
-      if constexpr (sdirk_sens_ok<Mdl>()) {
-#define DSH_SDIRK_SENS_LAUNCH(BA, WAVE, S)                                                                                                                              \
-  hipLaunchKernelGGL((k_sdirk_resident<Mdl, BA, WAVE, S, true>), grid, blk, 0, ctx->stream, nb, p, atol, (const SdirkConsts*)consts_dev, (const double*)t_eval_dev, \
-                     y_out, stats, status, t_root, root_idx, ncols, totals_dev)
-#define DSH_SDIRK_SENS_LAUNCH_S(BA, WAVE) do { if (method == 1) DSH_SDIRK_SENS_LAUNCH(BA, WAVE, 3); else DSH_SDIRK_SENS_LAUNCH(BA, WAVE, 4); } while (0)
-        if (ba) { if (wave) DSH_SDIRK_SENS_LAUNCH_S(true, true); else DSH_SDIRK_SENS_LAUNCH_S(true, false); }
-        else { if (wave) DSH_SDIRK_SENS_LAUNCH_S(false, true); else DSH_SDIRK_SENS_LAUNCH_S(false, false); }
-#undef DSH_SDIRK_SENS_LAUNCH_S
-#undef DSH_SDIRK_SENS_LAUNCH
-      }
+      if constexpr (sdirk_sens_ok<Mdl>())
+        with_bools_stages(ba, wave, method == 1 ? 3 : 4, [&](auto BA, auto WAVE, auto S) {
+          hipLaunchKernelGGL((k_sdirk_resident<Mdl, decltype(BA)::value, decltype(WAVE)::value, decltype(S)::value, true>), grid, blk, 0, ctx->stream, nb, a.p, a.atol,
+                             consts_dev, L.t_eval, a.y_out, a.stats, a.status, a.t_root, a.root_idx, a.ncols, L.totals);
+        });
     });
   } else
   dispatch_static_model(model, size, [&](auto mdl) {
     using Mdl = decltype(mdl);
-    if constexpr (Mdl::N <= 4) {
-#define DSH_SDIRK_LAUNCH(BA, WAVE, S)                                                                                                                         \
-  hipLaunchKernelGGL((k_sdirk_resident<Mdl, BA, WAVE, S>), grid, blk, 0, ctx->stream, nb, p, atol, (const SdirkConsts*)consts_dev, (const double*)t_eval_dev, \
-                     y_out, stats, status, t_root, root_idx, ncols, totals_dev)
-#define DSH_SDIRK_LAUNCH_S(BA, WAVE) do { if (method == 1) DSH_SDIRK_LAUNCH(BA, WAVE, 3); else DSH_SDIRK_LAUNCH(BA, WAVE, 4); } while (0)
-      if (ba) { if (wave) DSH_SDIRK_LAUNCH_S(true, true); else DSH_SDIRK_LAUNCH_S(true, false); }
-      else { if (wave) DSH_SDIRK_LAUNCH_S(false, true); else DSH_SDIRK_LAUNCH_S(false, false); }
-#undef DSH_SDIRK_LAUNCH_S
-#undef DSH_SDIRK_LAUNCH
-    }
+    if constexpr (Mdl::N <= 4)
+      with_bools_stages(ba, wave, method == 1 ? 3 : 4, [&](auto BA, auto WAVE, auto S) {
+        hipLaunchKernelGGL((k_sdirk_resident<Mdl, decltype(BA)::value, decltype(WAVE)::value, decltype(S)::value>), grid, blk, 0, ctx->stream, nb, a.p, a.atol, consts_dev,
+                           L.t_eval, a.y_out, a.stats, a.status, a.t_root, a.root_idx, a.ncols, L.totals);
+      });
   });
-  DSH_HIP_CHECK(hipGetLastError());
-  DSH_HIP_CHECK(timing_end(ctx));
-  unsigned long long totals[8] = {0};
-  DSH_HIP_CHECK(hipMemcpyAsync(totals, totals_dev, sizeof(unsigned long long) * 6, hipMemcpyDeviceToHost, ctx->stream));
-  DSH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  DSH_HIP_CHECK(timing_collect(ctx));
-  dsh_free(ctx, t_eval_dev);
-  dsh_free(ctx, totals_dev);
-  dsh_free(ctx, consts_dev);
-  if (totals_host) for (int q = 0; q < 6; ++q) totals_host[q] = (int64_t)totals[q];
-  return DSH_OK;
+  return L.close(a.totals_host);
 }
 }  // namespace

@@ -180,6 +180,10 @@ DEVICE_ABI = {
     "dsh_erk_solve_resident_steps": (cint, [vp, cint, cint, i64, i64, vp, vp, i64, dbl, dbl, dbl, vp, dbl, i64, vp, vp, vp, vp, vp, vp, vp, c_i64p]),
     "dsh_erk_model_has_sens": (cint, [cint, i64]),
     "dsh_erk_solve_resident_sens": (cint, [vp, cint, cint, i64, i64, vp, vp, i64, dbl, dbl, dbl, vp, c_dp, i64, dbl, c_dp, i64, vp, vp, vp, vp, c_i64p]),
+    "dsh_erk_model_has_out_integral": (cint, [cint, i64]),
+    "dsh_erk_model_nout": (i64, [cint, i64]),
+    "dsh_erk_solve_resident_out": (cint, [vp, cint, cint, i64, i64, vp, vp, i64, dbl, dbl, dbl, vp, c_dp, i64, dbl, c_dp, i64, vp, vp, vp, vp, vp, vp, c_i64p]),
+    "dsh_erk_solve_resident_steps_out": (cint, [vp, cint, cint, i64, i64, vp, vp, i64, dbl, dbl, dbl, vp, dbl, i64, dbl, c_dp, i64, vp, vp, vp, vp, vp, vp, vp, c_i64p]),
     "dsh_model_has_adaptive_sens": (cint, [cint, i64]),
     "dsh_model_has_adaptive_reset": (cint, [cint, i64]),
     "dsh_sdirk_solve_resident_sens": (cint, [vp, cint, cint, i64, i64, vp, vp, i64, dbl, dbl, dbl, vp, c_dp, i64, dbl, c_dp, i64, vp, vp, vp, vp, c_i64p]),
@@ -220,6 +224,8 @@ HOST_ABI = {
     "dshs_create_sens": (cint, [cint, vp, cint, i64, i64, c_dp, i64, dbl, c_dp, i64, dbl, dbl, cint, C.POINTER(DshsOptions), cint, dbl, c_dp, i64, C.POINTER(vp)]),
     "dshs_destroy": (None, [vp]),
     "dshs_nparams": (i64, [vp]),
+    "dshs_set_integrate_out": (cint, [vp, cint, dbl, c_dp, i64]),
+    "dshs_nout": (i64, [vp]),
     "dshs_interpolate_sens": (cint, [vp, dbl, c_dp]),
     "dshs_reset": (cint, [vp]),
     "dshs_context": (vp, [vp]),

@@ -49,6 +49,11 @@ struct ErkConsts {
   double* sens_out;
   double sens_rtol, sens_atol[4];
   int sens_error_control, sens_pad;
+  // Integrated outputs (k_erk_resident<.., INTOUT = true>; OdeBuilder::integrate_out(true)): g(t) = integral of out(y, t) carried by the solver state, y_out holds g.
+  // out_error_control != 0 (output tolerances were given, output_in_error_control): g takes part in the error test with out_rtol / out_atol, else it does not;
+  // out_pad = 1: out_atol[0] for every output.  Appended: a kernel without integrated outputs never reads them.
+  double out_rtol, out_atol[8];
+  int out_error_control, out_pad;
 };
 
 // Doubles a lane keeps: 14 N without sensitivities (7 stage increments, y, dy, old_y, stage point, stage derivative, error vector, atol), 12 N more per parameter
@@ -56,6 +61,22 @@ struct ErkConsts {
 // scratch memory; a model with forward sensitivities is admitted up to the same count.
 constexpr int kErkMaxLaneDoubles = 112;
 __host__ __device__ constexpr bool erk_sens_admitted(int64_t n, int64_t np) { return n >= 1 && np >= 1 && n * (14 + 12 * np) <= kErkMaxLaneDoubles; }
+// Integrated outputs (INTOUT): 12 doubles more per output (7 increments, g, old_g, dg, the error entry, out_atol), within the same count; at most 8 outputs
+// (ErkConsts::out_atol).  nout_e: the model's out_i count, or its state count when it has none (identity output).  No sensitivities; root functions are allowed.
+constexpr int kErkMaxOut = 8;
+__host__ __device__ constexpr bool erk_out_admitted(int64_t n, int64_t nout_e) {
+  return n >= 1 && nout_e >= 1 && nout_e <= kErkMaxOut && 14 * n + 12 * nout_e <= kErkMaxLaneDoubles;
+}
+template <class Mdl> constexpr int erk_nout_e() { return model_nout<Mdl>::value > 0 ? model_nout<Mdl>::value : Mdl::N; }
+// out(y, t): out_i of the model, the state itself for a model without (state.rs:1097-1103)
+template <class Mdl, int NO>
+__device__ __forceinline__ void erk_out(double t, const double (&y)[Mdl::N], const double (&p)[Mdl::NP], double (&o)[NO]) {
+  if constexpr (model_nout<Mdl>::value > 0) Mdl::out(t, y, p, o);
+  else {
+DSH_UNROLL_N
+    for (int i = 0; i < NO; ++i) o[i] = y[i];
+  }
+}
 
 // The two halves of interpolate_inplace (runge_kutta.rs:968-981 interpolate_beta_function, :962-966 interpolate_from_diff) apart, for the kernel with sensitivities:
 // the beta function of a save point is computed once and applied to the state and to every sensitivity (interpolate_sens_inplace, :1237-1309).  The operations and
@@ -91,7 +112,9 @@ DSH_UNROLL_N
 // The register allocator picks the occupancy (no waves-per-SIMD attribute): see DESIGN.md for the compiler's numbers.
 // SENS: ExplicitRk<.., SensEquations> — per parameter j the stage increments sdiff_j, s_j, ds_j, old_s_j and the stage point and its derivative, all in registers
 // (every loop over the parameters is unrolled: no array is indexed at run time); models within erk_sens_admitted() only.
-template <class Mdl, bool BA, bool WAVE, bool SENS = false>
+// INTOUT: problem.integrate_out — g = integral of out(y, t), with its own stage increments gdiff, carried like the state (runge_kutta.rs:529-533, :568-575, :802-810,
+// :900-909, :1185-1235); y_out holds g, NOUT_E rows per column in place of N; models within erk_out_admitted() only, without SENS.
+template <class Mdl, bool BA, bool WAVE, bool SENS = false, bool INTOUT = false>
 __global__ __launch_bounds__(64) void k_erk_resident(int64_t nb, const double* __restrict__ p_g, const double* __restrict__ atol_g, const ErkConsts* __restrict__ Cp,
                                                      const double* __restrict__ t_eval, double* __restrict__ y_out, int32_t* __restrict__ stats_out,
                                                      int32_t* __restrict__ status_out, double* __restrict__ t_root_out, int32_t* __restrict__ root_idx_out,
@@ -100,6 +123,7 @@ __global__ __launch_bounds__(64) void k_erk_resident(int64_t nb, const double* _
   static_assert(!Mdl::HAS_MASS, "explicit Runge-Kutta methods take no mass matrix (MassMatrixNotSupported, runge_kutta.rs:236-239)");
   static_assert(!SENS || Mdl::NROOTS == 0, "device-resident Tsit45 with forward sensitivities: models without root functions");
   static_assert(!SENS || erk_sens_admitted(Mdl::N, Mdl::NP), "device-resident Tsit45 with forward sensitivities: N (14 + 12 NP) <= 112 doubles per lane");
+  static_assert(!INTOUT || (!SENS && erk_out_admitted(Mdl::N, erk_nout_e<Mdl>())), "device-resident Tsit45 with integrated outputs: 14 N + 12 NOUT <= 112 doubles per lane, NOUT <= 8, no sensitivities");
   const ErkConsts& T = *Cp;
   const ResidentConsts& C = T.r;
   const dsh_adaptive_options& o = C.o;
@@ -165,6 +189,21 @@ DSH_UNROLL_N
     }
   }
 
+  // ------------------------------------------------------------ integrate_out (state.rs:1097-1109): g = 0, dg = out(y0, t0); gdiff starts at zero like diff
+  constexpr int NO = INTOUT ? erk_nout_e<Mdl>() : 1, SO = INTOUT ? S : 1;
+  double gdiff[SO][NO], g[NO], old_g[NO], dg[NO], o_atol[NO];
+  double sdg[NO];  // old_state.dg: out at the stage point (declared here for the reason given at ss / sds)
+  if constexpr (INTOUT) {
+    erk_out<Mdl, NO>(t, y, p, dg);
+#pragma unroll
+    for (int k = 0; k < NO; ++k) {
+      g[k] = 0.0; old_g[k] = 0.0;
+      o_atol[k] = T.out_atol[T.out_pad != 0 ? 0 : k];
+#pragma unroll
+      for (int q = 0; q < S; ++q) gdiff[q][k] = 0.0;
+    }
+  }
+
   // handle_tstop (runge_kutta.rs:752-781): 0 nothing, 1 reached, 2 StopTimeBeforeCurrentTime
   bool has_tstop = true;
   const double tstop = t_eval[C.n_eval - 1];
@@ -215,6 +254,25 @@ DSH_UNROLL_N
     }
     col++;
   };
+  // the same two writers with g in the column (INTOUT): NO rows
+  auto steps_write_g = [&](double tw, const double (&gw)[NO]) __attribute__((always_inline)) {
+    if (col < T.steps_cap && active) {
+      T.steps_t_out[(int64_t)col * nb + b] = tw;
+#pragma unroll
+      for (int k = 0; k < NO; ++k) y_out[((int64_t)col * NO + k) * nb + b] = gw[k];
+    }
+    col++;
+  };
+  // interpolate_out_inplace (runge_kutta.rs:1185-1235): the beta function of the save point applied to (old_g, gdiff)
+  auto interpolate_g = [&](double tt, double (&ret)[NO]) __attribute__((always_inline)) {
+    if constexpr (INTOUT) {
+      double bf[S];
+      erk_beta_function(t, old_t, tt, bf);
+      erk_from_diff<NO>(bf, old_g, gdiff, ret);
+    }
+  };
+  if constexpr (INTOUT) { if (steps_mode) steps_write_g(t, g); }  // write_out before the first step: state.g = 0
+  else
   if (steps_mode) steps_write(t, y);  // write_out before the first step (method.rs:900)
   {  // set_stop_time (runge_kutta.rs:436-444); t_eval[0] >= t0 is checked on the host
     const int r = handle_tstop();
@@ -241,6 +299,10 @@ DSH_UNROLL_N
 DSH_UNROLL_N
           for (int r = 0; r < N; ++r) sdiff[j][0][r] = hh * ds[j][r];
       }
+      if constexpr (INTOUT) {  // :529-533
+#pragma unroll
+        for (int k = 0; k < NO; ++k) gdiff[0][k] = hh * dg[k];
+      }
 #pragma unroll
       for (int i = 1; i < S; ++i) {
         // do_stage (runge_kutta.rs:537-566): old_state.y = y + diff[:, 0..i] a_row_i (nalgebra gemv order), diff[:, i] = h f(old_state.y, t + c_i h)
@@ -255,6 +317,11 @@ DSH_UNROLL_N
         Mdl::rhs(ts, sy, p, sdy);
 DSH_UNROLL_N
         for (int r = 0; r < N; ++r) diff[i][r] = hh * sdy[r];
+        if constexpr (INTOUT) {  // :568-575: old_state.dg = out(old_state.y, t + c_i h), gdiff[:, i] = h old_state.dg
+          erk_out<Mdl, NO>(ts, sy, p, sdg);
+#pragma unroll
+          for (int k = 0; k < NO; ++k) gdiff[i][k] = hh * sdg[k];
+        }
         if constexpr (SENS) {  // :578-607: SensRhs about the stage point (sy, ts); old_state.s_j = s_j + sdiff_j[:, 0..i] a_row_i, sdiff_j[:, i] = h SensRhs(old_state.s_j)
 #pragma unroll
           for (int j = 0; j < NP; ++j) {
@@ -285,6 +352,19 @@ DSH_UNROLL_N
         err[r] = acc;
       }
       error_norm = fmax(0.0, group_norm<WAVE>(wms<N>(err, y, atol, rtol)));
+      if constexpr (INTOUT) {  // :802-810: gdiff d against state.g (the g at the start of the step) with the output tolerances, after the states' norm
+        if (T.out_error_control) {
+          double oerr[NO];
+#pragma unroll
+          for (int k = 0; k < NO; ++k) {
+            double acc = 1.0 * gdiff[0][k] * kTsitD[0];
+#pragma unroll
+            for (int q = 1; q < S; ++q) acc = 1.0 * gdiff[q][k] * kTsitD[q] + acc;
+            oerr[k] = acc;
+          }
+          error_norm = fmax(error_norm, group_norm<WAVE>(wms<NO>(oerr, g, o_atol, T.out_rtol)));
+        }
+      }
       if constexpr (SENS) {  // :812-822: scaled by state.s_j at the start of the step; the states' norm, then j = 0, 1, ..
         if (T.sens_error_control) {
 #pragma unroll
@@ -321,6 +401,15 @@ DSH_UNROLL_N
     prev_err = error_norm; has_prev_err = true;
     // ---- step_accepted(h, h * factor, rescale_dy = false) (runge_kutta.rs:894-960): old_state <- (last stage point, its derivative, t + h, new_h); swap
     {
+      if constexpr (INTOUT) {  // :900-909: old_state.g = state.g + gdiff b, then the swap (which takes the last stage's dg along)
+#pragma unroll
+        for (int k = 0; k < NO; ++k) {
+          double acc = 1.0 * gdiff[0][k] * kTsitB[0] + 1.0 * g[k];
+#pragma unroll
+          for (int q = 1; q < S; ++q) acc = 1.0 * gdiff[q][k] * kTsitB[q] + acc;
+          old_g[k] = g[k]; g[k] = acc; dg[k] = sdg[k];
+        }
+      }
 DSH_UNROLL_N
       for (int r = 0; r < N; ++r) { old_y[r] = y[r]; y[r] = sy[r]; dy[r] = sdy[r]; }
       if constexpr (SENS) {
@@ -348,8 +437,16 @@ DSH_UNROLL_N
     }
     // ================================================================ solve_dense (method.rs:467-520) / solve (:881-961)
     const double upto = reason == 3 ? t_root : t;
-    if (steps_mode) {  // InternalTimestep / TstopReached -> write_out: state.y; a root is written below, at the root
-      if (reason != 3) steps_write(t, y);
+    if (steps_mode) {  // InternalTimestep / TstopReached -> write_out: state.y (state.g with INTOUT); a root is written below, at the root
+      if (reason != 3) { if constexpr (INTOUT) steps_write_g(t, g); else steps_write(t, y); }
+    } else if constexpr (INTOUT) {
+      while (col < C.n_eval && t_eval[col] <= upto) {
+        double gv[NO];
+        interpolate_g(t_eval[col], gv);
+#pragma unroll
+        for (int k = 0; k < NO; ++k) if (active) y_out[((int64_t)col * NO + k) * nb + b] = gv[k];
+        col++;
+      }
     } else
     while (col < C.n_eval && t_eval[col] <= upto) {
       double yv[N];
@@ -370,6 +467,19 @@ DSH_UNROLL_N
       for (int i = 0; i < N; ++i) if (active) y_out[((int64_t)col * N + i) * nb + b] = yv[i];
       col++;
     }
+    if (reason == 3 && INTOUT) {  // state_mut_back(t_root, integrate_out) (:396-434): g at the root goes where the state goes
+      if constexpr (INTOUT) {
+        double gv[NO];
+        interpolate_g(t_root, gv);
+        if (steps_mode) steps_write_g(t_root, gv);
+        else if (col < C.n_eval) {
+#pragma unroll
+          for (int k = 0; k < NO; ++k) if (active) y_out[((int64_t)col * NO + k) * nb + b] = gv[k];
+          col++;
+        }
+      }
+      done = true;
+    } else
     if (reason == 3) {  // state_mut_back(t_root): the column after the drained ones holds the state at the root
       double yv[N];
       interpolate(t_root, yv);
@@ -387,6 +497,10 @@ DSH_UNROLL_N
     if (ncols_out != nullptr) ncols_out[b] = col;
     if (!steps_mode)
     for (; col < C.n_eval; ++col) {  // columns that were never reached (root stop or error exit): NaN
+      if constexpr (INTOUT) {
+#pragma unroll
+        for (int k = 0; k < NO; ++k) y_out[((int64_t)col * NO + k) * nb + b] = __builtin_nan("");
+      } else
 DSH_UNROLL_N
       for (int i = 0; i < N; ++i) y_out[((int64_t)col * N + i) * nb + b] = __builtin_nan("");
       if constexpr (SENS) {

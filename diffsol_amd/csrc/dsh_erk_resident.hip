@@ -9,6 +9,10 @@
 //
 // Arithmetic is the checker's operation for operation (tests/erk_ref/erk_ref.cpp over the oracle's vector operations); compiled without contraction.  There is no
 // fast-arithmetic twin: deterministic_pow = 2 runs this kernel with the portable pow, like 1.
+//
+// Two trailing template flags add to the lane's state, each for the models its admission function takes: SENS the forward sensitivities of every parameter
+// (dsh_erk_solve_resident_sens), INTOUT the integral g of the output equations, returned in place of the states (dsh_erk_solve_resident_out / _steps_out; checker
+// tests/erk_out_ref/erk_out_ref.cpp).  With both off the kernel is the plain one, instruction for instruction.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -53,6 +57,28 @@ int erk_model_has_sens(int model, int64_t size) {
   dispatch_static_model(model, size, [&](auto mdl) { ok = erk_sens_ok<decltype(mdl)>(); });
   return ok ? 1 : 0;
 }
+// Tsit45 with integrated outputs (k_erk_resident<.., INTOUT = true>): the models of the plain kernel whose states and outputs keep 14 n + 12 nout <= 112 doubles per
+// lane, nout <= 8 (erk_out_admitted, dsh_erk_kernel.hpp); nout is the out_i count, or the state count for a model without out_i (identity output)
+template <class Mdl> constexpr bool erk_out_ok() { return Mdl::N <= 4 && !Mdl::HAS_MASS && !model_has_reset<Mdl>::value && erk_out_admitted(Mdl::N, erk_nout_e<Mdl>()); }
+int64_t erk_model_nout_e(int model, int64_t size) {
+  if (is_jit_model(model)) {
+    const JitInfo* ji = jit_info(model);
+    return ji ? (ji->nout > 0 ? ji->nout : ji->n) : 0;
+  }
+  int64_t v = 0;
+  dispatch_static_model(model, size, [&](auto mdl) { v = erk_nout_e<decltype(mdl)>(); });
+  return v;
+}
+int erk_model_has_out_integral(int model, int64_t size) {
+  if (!erk_model_has_resident(model, size)) return 0;
+  if (is_jit_model(model)) {
+    const JitInfo* ji = jit_info(model);
+    return (ji && erk_out_admitted(ji->n, erk_model_nout_e(model, size))) ? 1 : 0;
+  }
+  bool ok = false;
+  dispatch_static_model(model, size, [&](auto mdl) { ok = erk_out_ok<decltype(mdl)>(); });
+  return ok ? 1 : 0;
+}
 }  // namespace dsh
 
 namespace {
@@ -80,6 +106,18 @@ int erk_refuse_sens(int model, int64_t size) {
             std::to_string(n * (14 + 12 * np)) + " doubles) and " + std::to_string(nroots) + " root functions: use BDF, TR-BDF2 or ESDIRK34 for its sensitivities");
   return DSH_E_UNSUPPORTED;
 }
+// a model the plain kernel takes, refused with integrated outputs
+int erk_refuse_out(int model, int64_t size) {
+  int64_t n = 0, np = 0, nroots = 0;
+  int has_mass = 0;
+  (void)dsh_model_info(model, size, &n, &np, &has_mass, &nroots);
+  const int64_t no = erk_model_nout_e(model, size);
+  set_error("dsh_erk_solve_resident_out: Tsit45 integrates outputs register-resident only — models whose states and outputs satisfy 14 * nstates + 12 * nout <= " +
+            std::to_string(kErkMaxLaneDoubles) + " doubles per member with nout <= " + std::to_string(kErkMaxOut) + " (for example 4 states and 4 outputs, 7 states and 1 output, "
+            "2 states and 7 outputs; a model without out_i integrates its states); this model has " + std::to_string(n) + " states and " + std::to_string(no) + " outputs (" +
+            std::to_string(14 * n + 12 * no) + " doubles): integrate fewer outputs, or append the integrals as states and use BDF, TR-BDF2 or ESDIRK34");
+  return DSH_E_UNSUPPORTED;
+}
 
 int erk_solve_resident_impl(const SolveArgs& a, int method) {
   static const char* const who = "dsh_erk_solve_resident";
@@ -91,6 +129,16 @@ int erk_solve_resident_impl(const SolveArgs& a, int method) {
   const bool sens = a.sens != nullptr;
   if (!erk_model_has_resident(model, size)) return erk_refuse(model, size);
   if (sens && !erk_model_has_sens(model, size)) return erk_refuse_sens(model, size);
+  const bool intout = a.intout != nullptr;
+  DSH_REQUIRE_AS(who, !(sens && intout), "integrated outputs are not combined with forward sensitivities");
+  if (intout && !erk_model_has_out_integral(model, size)) return erk_refuse_out(model, size);
+  if (intout) {
+    const int64_t no = erk_model_nout_e(model, size);
+    DSH_REQUIRE_AS(who, a.intout->natol == 0 || a.intout->natol == 1 || a.intout->natol == no,
+                   "out_atol must have length 1 or nout (" + std::to_string(no) + " for this model), or 0 to keep the outputs out of the error test; got " +
+                       std::to_string(a.intout->natol));
+    DSH_REQUIRE_AS(who, a.intout->natol == 0 || a.intout->atol_host != nullptr, "out_atol is null");
+  }
   if (nb == 0) return DSH_OK;
   ErkConsts T;
   std::memset((void*)&T, 0, sizeof T);
@@ -100,6 +148,11 @@ int erk_solve_resident_impl(const SolveArgs& a, int method) {
   T.min_shrink = 0.5; T.max_shrink = 1.0; T.min_growth = 1.0; T.max_growth = 2.0;
   fill_steps(T, a.steps);
   if (const int rc = fill_sens(T, a.sens, model, size, false, who); rc != DSH_OK) return rc;  // admitted models with parameters have at most 4 states
+  if (intout) {  // the kernel's NOUT_E is at most 8 (erk_out_admitted)
+    const OutSpec& os = *a.intout;
+    T.out_rtol = os.rtol; T.out_error_control = os.natol > 0 ? 1 : 0; T.out_pad = os.natol <= 1 ? 1 : 0;
+    for (int64_t k = 0; k < os.natol && k < kErkMaxOut; ++k) T.out_atol[k] = os.atol_host[k];
+  }
   const bool ba = a.atol_nb == 1 && nb != 1;
   const bool wave = T.r.o.group == 64;
   const dim3 grid((unsigned)((nb + 63) / 64)), blk(64);  // 64 members per wavefront in both modes
@@ -107,10 +160,19 @@ int erk_solve_resident_impl(const SolveArgs& a, int method) {
   if (const int rc = L.open(&T, sizeof T, a.t_eval_host, a.n_eval); rc != DSH_OK) return rc;
   const ErkConsts* const consts_dev = (const ErkConsts*)L.consts;
   if (is_jit_model(model)) {
-    const std::string name = std::string("dsh::k_erk_resident<dsh::JitModel, ") + (ba ? "true" : "false") + ", " + (wave ? "true" : "false") + (sens ? ", true>" : ">");
+    const std::string name = std::string("dsh::k_erk_resident<dsh::JitModel, ") + (ba ? "true" : "false") + ", " + (wave ? "true" : "false") + (sens ? ", true>" : (intout ? ", false, true>" : ">"));
     const int rc = jit_launch(ctx, model, "dsh_erk_kernel.hpp", name, {name}, name, grid, blk, 0, nb, a.p, a.atol, consts_dev, L.t_eval, a.y_out, a.stats, a.status, a.t_root,
                               a.root_idx, a.ncols, L.totals);
     if (rc != DSH_OK) return rc;
+  } else if (intout) {
+    dispatch_static_model(model, size, [&](auto mdl) {
+      using Mdl = decltype(mdl);
+      if constexpr (erk_out_ok<Mdl>())
+        with_bools(ba, wave, [&](auto BA, auto WAVE) {
+          hipLaunchKernelGGL((k_erk_resident<Mdl, decltype(BA)::value, decltype(WAVE)::value, false, true>), grid, blk, 0, ctx->stream, nb, a.p, a.atol, consts_dev, L.t_eval,
+                             a.y_out, a.stats, a.status, a.t_root, a.root_idx, a.ncols, L.totals);
+        });
+    });
   } else if (sens) {
     dispatch_static_model(model, size, [&](auto mdl) {
       using Mdl = decltype(mdl);
@@ -166,6 +228,33 @@ int dsh_erk_solve_resident_steps(dsh_ctx* ctx, int method, int model, int64_t si
   const StepsSpec st{t_out, max_cols};
   return erk_solve_resident_impl({ctx, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, &t_final, 1, y_out, stats, status, t_root, root_idx, ncols, totals_host, nullptr, &st},
                                  method);
+}
+// rows of y_out in the *_out entries: the model's out_i count, its state count without out_i; 0 for a model Tsit45 does not take
+int64_t dsh_erk_model_nout(int model, int64_t size) { return erk_model_has_resident(model, size) ? erk_model_nout_e(model, size) : 0; }
+// 1 when dsh_erk_solve_resident_out / _steps_out take the model: see erk_model_has_out_integral above
+int dsh_erk_model_has_out_integral(int model, int64_t size) { return erk_model_has_out_integral(model, size); }
+// Tsit45 with the output equations integrated alongside the states (OdeBuilder::integrate_out(true) over problem.tsit45()): arguments as dsh_erk_solve_resident;
+// y_out n_eval x nout x nb holds g(t) = integral of out(y, t) from t0 (nout: the model's out_i count, its state count without out_i).  nout_atol = 0 keeps g out of the
+// error test, 1 gives one out_atol for every output, nout one each.  A model outside dsh_erk_model_has_out_integral: DSH_E_UNSUPPORTED.
+int dsh_erk_solve_resident_out(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol, double t0,
+                               double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double out_rtol, const double* out_atol_host,
+                               int64_t nout_atol, double* y_out, int32_t* stats, int32_t* status, double* t_root, int32_t* root_idx, int32_t* ncols, int64_t* totals_host) {
+  DSH_ENTER(ctx);
+  const OutSpec os{out_rtol, out_atol_host, nout_atol};
+  return erk_solve_resident_impl({ctx, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, t_eval_host, n_eval, y_out, stats, status, t_root, root_idx, ncols, totals_host,
+                                  nullptr, nullptr, &os}, method);
+}
+// the same for every accepted step (arguments as dsh_erk_solve_resident_steps): column 0 is g(t0) = 0
+int dsh_erk_solve_resident_steps_out(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol,
+                                     double t0, double h0, const dsh_adaptive_options* opts, double t_final, int64_t max_cols, double out_rtol, const double* out_atol_host,
+                                     int64_t nout_atol, double* y_out, double* t_out, int32_t* stats, int32_t* status, double* t_root, int32_t* root_idx, int32_t* ncols,
+                                     int64_t* totals_host) {
+  DSH_ENTER(ctx);
+  DSH_REQUIRE(max_cols >= 2 && max_cols <= 0x7fffffff && y_out != nullptr && t_out != nullptr && ncols != nullptr, "dsh_erk_solve_resident_steps_out: max_cols >= 2, y_out, t_out and ncols are needed");
+  const StepsSpec st{t_out, max_cols};
+  const OutSpec os{out_rtol, out_atol_host, nout_atol};
+  return erk_solve_resident_impl({ctx, model, size, nb, p, atol, atol_nb, rtol, t0, h0, opts, &t_final, 1, y_out, stats, status, t_root, root_idx, ncols, totals_host, nullptr, &st,
+                                  &os}, method);
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@
 namespace dsh {
 
 struct SensSpec { double* out; double rtol; const double* atol_host; int64_t natol; };  // forward sensitivities in the same launch (the *_sens entry points)
+struct OutSpec { double rtol; const double* atol_host; int64_t natol; };  // integrated outputs in place of the states (the Tsit45 *_out entry points); natol = 0: outside the error test
 struct StepsSpec { double* t_out; int64_t cap; };  // OdeSolverMethod::solve: every accepted step out (the *_steps entry points; steps_cap of the consts)
 
 // what every driver takes; the extern "C" entry points fill it
@@ -39,6 +40,7 @@ struct SolveArgs {
   int64_t* totals_host;
   const SensSpec* sens;
   const StepsSpec* steps;
+  const OutSpec* intout = nullptr;
 };
 
 // DSH_REQUIRE under the name of the public entry family instead of the enclosing function's

@@ -26,6 +26,12 @@ struct dshs_solver {
   bool fused = false;
   bool kernel_timing = false;
   int method = 0;
+  // OdeBuilder::integrate_out (dshs_set_integrate_out): the device-resident Tsit45 solves return g = integral of out(y, t) in place of the states
+  bool integrate_out = false;
+  double out_rtol = 0.0;
+  std::vector<double> out_atol;  // empty: the outputs stay out of the error test
+  int64_t nout_e = 0;            // rows of g: the model's out_i count, its state count without out_i
+  int64_t nrows() const { return integrate_out ? nout_e : problem.eqn->nstates(); }
   void make_solver() {
     solver.reset();
     bdf = nullptr;
@@ -401,7 +407,7 @@ void run_resident(dshs_solver* s, const double* t_eval, int64_t nt, int group, i
   const int64_t size = pk.size;
   const int method = pk.method;
   const bool wave_member = pk.wave_member;
-  const int64_t n = s->problem.eqn->nstates(), nb = s->ctx.nbatch();
+  const int64_t n = s->nrows(), nb = s->ctx.nbatch();  // rows of a column: the states, or the integrated outputs (dshs_set_integrate_out)
   dsh_adaptive_options o = adaptive_options_of(s, group, deterministic_pow);
   dsh_ctx* c = s->ctx.raw();
   const bool sorted = group == 1 && prepare_member_order(s);
@@ -461,6 +467,10 @@ void run_resident(dshs_solver* s, const double* t_eval, int64_t nt, int group, i
   else if (wave_member)
     rc = dsh_bdf_solve_wave_member(c, model, size, nb, params_dev, s->problem.atol.ptr(), 1, s->problem.rtol, s->problem.t0, s->problem.h0, &o,
                                    t_eval, nt, out, (int32_t*)stats_dev, (int32_t*)status_dev, (double*)troot_dev, (int32_t*)ridx_dev, (int32_t*)ncols_dev, totals);
+  else if (method == 3 && s->integrate_out)
+    rc = dsh_erk_solve_resident_out(c, method, model, size, nb, params_dev, s->problem.atol.ptr(), 1, s->problem.rtol, s->problem.t0, s->problem.h0, &o, t_eval, nt, s->out_rtol,
+                                    s->out_atol.data(), (int64_t)s->out_atol.size(), out, (int32_t*)stats_dev, (int32_t*)status_dev, (double*)troot_dev, (int32_t*)ridx_dev,
+                                    (int32_t*)ncols_dev, totals);
   else if (method == 3)
     rc = dsh_erk_solve_resident(c, method, model, size, nb, params_dev, s->problem.atol.ptr(), 1, s->problem.rtol, s->problem.t0, s->problem.h0, &o, t_eval, nt, out,
                                 (int32_t*)stats_dev, (int32_t*)status_dev, (double*)troot_dev, (int32_t*)ridx_dev, (int32_t*)ncols_dev, totals);
@@ -656,6 +666,38 @@ int dshs_get_state(dshs_solver* s, double* t, double* h, int* order, double* y_h
   });
 }
 int64_t dshs_nparams(const dshs_solver* s) { return s->problem.eqn->nparams(); }
+int64_t dshs_nout(const dshs_solver* s) { return s->nrows(); }
+// OdeBuilder::integrate_out(on) with out_rtol / out_atol (nout_atol = 0: no output tolerances): see include/diffsol_hip_solver.h
+int dshs_set_integrate_out(dshs_solver* s, int on, double out_rtol, const double* out_atol, int64_t nout_atol) {
+  return guarded([&]() {
+    if (!s) throw LaError(DSH_E_INVALID, "dshs_set_integrate_out: null solver");
+    if (!on) { s->integrate_out = false; s->out_atol.clear(); return 0; }
+    static const char* const supported = "integrate_out is provided by the device-resident Tsit45 (dshs_solve_dense, dshs_solve_dense_adaptive, dshs_solve_adaptive of a "
+                                         "DSHS_METHOD_TSIT45 solver created without sensitivities, models with 14 * nstates + 12 * nout <= 112 and nout <= 8)";
+    if (s->method != DSHS_METHOD_TSIT45)
+      throw LaError(DSH_E_UNSUPPORTED, std::string("dshs_set_integrate_out: a BDF / TR-BDF2 / ESDIRK34 solver does not integrate its outputs — ") + supported +
+                                           "; with these methods append the integral as a state of the model");
+    if (s->problem.sens)
+      throw LaError(DSH_E_UNSUPPORTED, std::string("dshs_set_integrate_out: this solver was created with forward sensitivities, which are not combined with integrated outputs — ") +
+                                           supported);
+    int m = 0; int64_t sz = 0;
+    if (!s->problem.eqn->registry_model(&m, &sz)) throw LaError(DSH_E_UNSUPPORTED, std::string("dshs_set_integrate_out: the model has no device form — ") + supported);
+    const int64_t no = dsh_erk_model_nout(m, sz), ns = s->problem.eqn->nstates();
+    if (!dsh_erk_model_has_out_integral(m, sz))
+      throw LaError(DSH_E_UNSUPPORTED, "dshs_set_integrate_out: this model has " + std::to_string(ns) + " states and " + std::to_string(no) + " outputs (" +
+                                           std::to_string(14 * ns + 12 * no) + " doubles per member) — " + supported +
+                                           ": integrate fewer outputs, or append the integrals as states and use BDF, TR-BDF2 or ESDIRK34");
+    if (nout_atol != 0 && nout_atol != 1 && nout_atol != no)
+      throw LaError(DSH_E_INVALID, "dshs_set_integrate_out: out_atol must have length 1 or nout (" + std::to_string(no) + " for this model), or 0 for no output tolerances; got " +
+                                       std::to_string(nout_atol));
+    if (nout_atol > 0 && !out_atol) throw LaError(DSH_E_INVALID, "dshs_set_integrate_out: out_atol is null");
+    s->integrate_out = true;
+    s->nout_e = no;
+    s->out_rtol = out_rtol;
+    s->out_atol.assign(out_atol, out_atol + nout_atol);
+    return 0;
+  });
+}
 int dshs_interpolate_sens(dshs_solver* s, double t, double* s_host) {
   return guarded_flushed(s, [&]() {
     if (s->method == DSHS_METHOD_TSIT45 && s->problem.sens) throw LaError(DSH_E_UNSUPPORTED, kTsit45HostDriven);  // the sensitivities exist inside the resident launch only
@@ -890,7 +932,7 @@ int dshs_solve_adaptive(dshs_solver* s, double t_final, int64_t max_cols, int gr
     if (!pk.ok || (!sdirk && !erk && !pk.wave_member && !dsh_model_has_adaptive_steps(pk.model, pk.size)))
       throw LaError(DSH_E_UNSUPPORTED, "dshs_solve_adaptive: no device-resident integrator that writes every step for this model and method (register-resident static models, banded lane-per-member forms, "
                                        "wavefront / workgroup per member); dshs_solve returns every step of the host-driven lock-step solver");
-    const int64_t n = s->problem.eqn->nstates(), nb = s->ctx.nbatch();
+    const int64_t n = s->nrows(), nb = s->ctx.nbatch();
     const dsh_adaptive_options o = adaptive_options_of(s, group, deterministic_pow);
     dsh_ctx* c = s->ctx.raw();
     void *y_dev = nullptr, *t_dev = nullptr, *stats_dev = nullptr, *status_dev = nullptr, *troot_dev = nullptr, *ridx_dev = nullptr, *ncols_dev = nullptr;
@@ -906,6 +948,11 @@ int dshs_solve_adaptive(dshs_solver* s, double t_final, int64_t max_cols, int gr
     if (t_root_host) check(dsh_malloc(c, (int64_t)sizeof(double) * nb, 0, &troot_dev), "solve_adaptive t_root");
     if (root_idx_host) check(dsh_malloc(c, (int64_t)sizeof(int32_t) * nb, 0, &ridx_dev), "solve_adaptive root_idx");
     int64_t tot[6] = {0};
+    if (erk && s->integrate_out)
+      check(dsh_erk_solve_resident_steps_out(c, pk.method, pk.model, pk.size, nb, s->problem.eqn->params().ptr(), s->problem.atol.ptr(), 1, s->problem.rtol, s->problem.t0, s->problem.h0, &o,
+                                             t_final, max_cols, s->out_rtol, s->out_atol.data(), (int64_t)s->out_atol.size(), (double*)y_dev, (double*)t_dev, (int32_t*)stats_dev,
+                                             (int32_t*)status_dev, (double*)troot_dev, (int32_t*)ridx_dev, (int32_t*)ncols_dev, tot), "dsh_erk_solve_resident_steps_out");
+    else
     if (erk)
       check(dsh_erk_solve_resident_steps(c, pk.method, pk.model, pk.size, nb, s->problem.eqn->params().ptr(), s->problem.atol.ptr(), 1, s->problem.rtol, s->problem.t0, s->problem.h0, &o,
                                          t_final, max_cols, (double*)y_dev, (double*)t_dev, (int32_t*)stats_dev, (int32_t*)status_dev, (double*)troot_dev, (int32_t*)ridx_dev,

@@ -51,7 +51,7 @@ class Solver:
     """One ensemble solver instance on one GPU."""
 
     def __init__(self, model, p, *, nbatch=1, model_size=0, rtol=1e-6, atol=(1e-6,), t0=0.0, h0=1.0, method=METHOD_BDF, device=0, stream=None,
-                 fused=True, block_threads=0, options=None, ensemble_mode=None, sens=False, sens_rtol=None, sens_atol=None, op_queue=False):
+                 fused=True, block_threads=0, options=None, ensemble_mode=None, sens=False, sens_rtol=None, sens_atol=None, op_queue=False, integrate_out=False, out_rtol=None, out_atol=None):
         L = _ffi.load_host_lib()
         self._L = L
         if isinstance(model, str):
@@ -83,10 +83,27 @@ class Solver:
         self.n = int(L.dshs_nstates(h))
         self.nbatch = int(L.dshs_nbatch(h))
         self.fused = bool(L.dshs_is_fused(h))
+        self.nout = self.n
+        if integrate_out:  # OdeBuilder::integrate_out(true): a refusal leaves no solver behind
+            try:
+                self.set_integrate_out(True, out_rtol, out_atol)
+            except Exception:
+                L.dshs_destroy(h)
+                self._h = None
+                raise
         if ensemble_mode is not None:
             self.set_ensemble_mode(ensemble_mode)
         if op_queue:
             self.set_op_queue(True)
+
+    def set_integrate_out(self, on, out_rtol=None, out_atol=None):
+        """dshs_set_integrate_out (OdeBuilder::integrate_out): solve_dense / solve_dense_adaptive / solve_adaptive of a Tsit45 solver return g = integral of out(y, t)
+        from t0, [.., nbatch, nout] with nout = self.nout (the model's out_i count, its state count without out_i).  out_atol None: no output tolerances, g stays out
+        of the error test; a scalar or [nout]: g takes part in it with out_rtol / out_atol."""
+        oa = np.zeros(0) if out_atol is None else np.ascontiguousarray(np.asarray(out_atol, dtype=np.float64).reshape(-1))
+        buf = oa if oa.size else np.zeros(1)
+        check(self._L.dshs_set_integrate_out(self._h, 1 if on else 0, 0.0 if out_rtol is None else float(out_rtol), buf.ctypes.data_as(_ffi.c_dp), oa.size), host=True)
+        self.nout = int(self._L.dshs_nout(self._h))
 
     OP_QUEUE_STATS = ("ops_enqueued", "chain_launches", "hazard_flushes", "entry_flushes")
 
@@ -218,7 +235,7 @@ class Solver:
 
     def solve_dense(self, t_eval, want_host=True, dev_ptr=None):
         te = np.ascontiguousarray(t_eval, dtype=np.float64)
-        out = np.empty((te.size, self.nbatch, self.n)) if want_host else None
+        out = np.empty((te.size, self.nbatch, self.nout)) if want_host else None   # nout = n unless integrate_out is on
         reason = C.c_int()
         check(self._L.dshs_solve_dense(self._h, te.ctypes.data_as(_ffi.c_dp), te.size, out.ctypes.data_as(_ffi.c_dp) if want_host else None,
                                        vp(dev_ptr) if dev_ptr else None, C.byref(reason)), host=True)
@@ -232,9 +249,9 @@ class Solver:
         """solve_dense with device-resident step-size/order control, the whole ensemble in ONE launch (dshs_solve_dense_adaptive):
         group=1 every member its own history and event time (CPU semantics of a sweep), group=64 wavefront-sized lock-step groups (batched
         semantics, nbatch 64).  deterministic_pow=True (default) uses the pow() of include/diffsol_detpow.h: bit-identical to the oracle in the same mode; False: ocml's pow().
-        Returns (y [nt, nbatch, n] or None, totals dict[, member dict(stats [5, nbatch], status, t_root, root_idx, ncols)])."""
+        Returns (y [nt, nbatch, n] or None, totals dict[, member dict(stats [5, nbatch], status, t_root, root_idx, ncols)]); with integrate_out y is g [nt, nbatch, nout]."""
         te = np.ascontiguousarray(t_eval, dtype=np.float64)
-        out = np.empty((te.size, self.nbatch, self.n)) if want_host else None
+        out = np.empty((te.size, self.nbatch, self.nout)) if want_host else None
         totals = (C.c_int64 * 6)()
         m = None
         if want_member_stats:
@@ -253,9 +270,9 @@ class Solver:
         """OdeSolverMethod::solve (method.rs:227-258) on the device-resident BDF (dshs_solve_adaptive): the state of every member after EVERY accepted step, the whole
         ensemble in one launch.  Returns (y [max_cols, nbatch, n], t [max_cols, nbatch], member dict(ncols, stats [5, nbatch], status, t_root, root_idx), totals dict);
         member b's solution is y[:ncols[b], b], t[:ncols[b], b] (column 0 = the initial state, the last one at t_final or at the member's event); ncols[b] > max_cols:
-        call again with more room."""
+        call again with more room.  With integrate_out y is g [max_cols, nbatch, nout], column 0 zero."""
         nb = self.nbatch
-        y = np.full((max_cols, nb, self.n), np.nan)
+        y = np.full((max_cols, nb, self.nout), np.nan)
         t = np.full((max_cols, nb), np.nan)
         m = dict(ncols=np.empty(nb, dtype=np.int32), stats=np.empty((5, nb), dtype=np.int32), status=np.empty(nb, dtype=np.int32), t_root=np.empty(nb),
                  root_idx=np.empty(nb, dtype=np.int32))
@@ -363,6 +380,10 @@ class OdeBuilder:
     def stream(self, v): self._kw["stream"] = v; return self
     def fused(self, v): self._kw["fused"] = v; return self
     def options(self, **kw): self._kw["options"] = kw; return self
+    # builder.rs integrate_out / out_rtol / out_atol: the Tsit45 solves return the integral of the outputs; tolerances put it into the error test
+    def integrate_out(self, v): self._kw["integrate_out"] = bool(v); return self
+    def out_rtol(self, v): self._kw["out_rtol"] = v; return self
+    def out_atol(self, v): self._kw["out_atol"] = tuple(np.atleast_1d(v)); return self
 
     def model(self, name, size=0):
         self._model = name

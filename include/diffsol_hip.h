@@ -610,6 +610,25 @@ int dsh_erk_model_has_sens(int model, int64_t size);
 int dsh_erk_solve_resident_sens(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol,
                                 double t0, double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double sens_rtol,
                                 const double* sens_atol_host, int64_t nsens_atol, double* y_out, double* sens_out, int32_t* stats, int32_t* status, int64_t* totals_host);
+/* Tsit45 with the OUTPUT EQUATIONS INTEGRATED alongside the states (OdeBuilder::integrate_out(true) over problem.tsit45(); the Rk core's output halves
+ * runge_kutta.rs:529-533, :568-575, :802-810, :900-909, :1185-1235, :396-434): the solver state carries g(t) = integral from t0 of out(y, t), and y_out holds g where
+ * dsh_erk_solve_resident / _steps put the states: n_eval (max_cols) x nout x nb, batch-fastest, columns a member never reached NaN, the column before the first step
+ * (steps) zero, at a root g interpolated at t_root.  nout is the model's out_i count, or its state count for a model without out_i (identity output).  Output
+ * tolerances: nout_atol = 0 keeps g out of the error test (the states and every counter are then those of the plain solve); 1 gives one out_atol for every output,
+ * nout one each (any other length: DSH_E_INVALID); the error of g is scaled by the g at the start of the step with out_rtol / out_atol and max-chained after the
+ * states' norm.  Models (dsh_erk_model_has_out_integral): those of dsh_model_has_resident(3, ..) with 14 * nstates + 12 * nout <= 112 doubles per member and
+ * nout <= 8 (4 states and 4 outputs, 7 states and 1, 2 states and 7, 1 state and 8); root functions are allowed, forward sensitivities are not combined; any other
+ * model: DSH_E_UNSUPPORTED.  The other arguments as dsh_erk_solve_resident / dsh_erk_solve_resident_steps. */
+int dsh_erk_model_has_out_integral(int model, int64_t size);
+int64_t dsh_erk_model_nout(int model, int64_t size); /* nout as above; 0 for a model outside dsh_model_has_resident(3, ..) */
+int dsh_erk_solve_resident_out(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol,
+                               double t0, double h0, const dsh_adaptive_options* opts, const double* t_eval_host, int64_t n_eval, double out_rtol,
+                               const double* out_atol_host, int64_t nout_atol, double* y_out, int32_t* stats, int32_t* status, double* t_root, int32_t* root_idx,
+                               int32_t* ncols, int64_t* totals_host);
+int dsh_erk_solve_resident_steps_out(dsh_ctx* ctx, int method, int model, int64_t size, int64_t nb, const double* p, const double* atol, int64_t atol_nb, double rtol,
+                                     double t0, double h0, const dsh_adaptive_options* opts, double t_final, int64_t max_cols, double out_rtol,
+                                     const double* out_atol_host, int64_t nout_atol, double* y_out, double* t_out, int32_t* stats, int32_t* status, double* t_root,
+                                     int32_t* root_idx, int32_t* ncols, int64_t* totals_host);
 
 
 /* ------------------------------------------------------------------------------------------------------------------------------------------------

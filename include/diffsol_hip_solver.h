@@ -96,6 +96,15 @@ int dshs_get_kernel_timing_overhead(dshs_solver* s, double* empty_bracket_ms, do
 int64_t dshs_nstates(const dshs_solver* s);
 int64_t dshs_nbatch(const dshs_solver* s);
 int dshs_is_fused(const dshs_solver* s);
+/* OdeBuilder::integrate_out(true) (+ out_rtol / out_atol): while the flag is on, dshs_solve_dense, dshs_solve_dense_adaptive and dshs_solve_adaptive of a Tsit45 solver
+ * return g(t) = integral from t0 of out(y, t) where they return the states otherwise, dshs_nout(s) rows per column ([col][b][nout] on the host, [col][nout][b] in
+ * y_dev): the model's out_i count, or its state count for a model without out_i (identity output).  At a root the column holds g at the root; every counter, status,
+ * t_root and ncols keep their meaning.  nout_atol = 0: no output tolerances, g stays out of the error test and the states are those of the plain solve bit for bit;
+ * nout_atol = 1 or nout: g takes part with out_rtol / out_atol (another length: DSH_E_INVALID).  Refused with DSH_E_UNSUPPORTED and a message that names what is
+ * supported: a BDF / TR-BDF2 / ESDIRK34 solver, a solver created with sensitivities, a model outside dsh_erk_model_has_out_integral (14 * nstates + 12 * nout <= 112,
+ * nout <= 8).  on = 0 switches back to the states.  dshs_nout: rows per column of those three entries as the flag stands (nstates while it is off). */
+int dshs_set_integrate_out(dshs_solver* s, int on, double out_rtol, const double* out_atol, int64_t nout_atol);
+int64_t dshs_nout(const dshs_solver* s);
 
 /* OdeSolverMethod::step / set_stop_time / interpolate / state  (method.rs:42-198) */
 int dshs_step(dshs_solver* s, int* stop_reason);

@@ -20,6 +20,12 @@
 // Its prediction, its update of the differences and the norms of its order selection have a body per order behind one scalar dispatch on the wavefront-uniform order
 // (with_order, dsh_adaptive_kernel.hpp) with that order's Bdf::_new coefficients as constants (dsh_bdf_tables.hpp): the same operations per component, the same bits
 // (profiles/order_paths.md, tests/test_gpu_order_paths.py).
+// Its wavefront maxima (the Newton norms from the second iteration on, the error norm, the order selection's norms) run a stage written as the instructions it needs:
+// two v_mov_b32_dpp and one v_max_f64 (dpp_max_f64_raw, dsh_adaptive_kernel.hpp).  The general stage is __builtin_fmax on a value put together from DPP moves, and in
+// IEEE mode the compiler puts a quieting v_max_f64 x, x, x in front of every such maximum: an instruction that is issued, sits on the reduction's serial chain and is
+// the identity on what these call sites reduce.  The stage is exact under their conditions: the values are weighted mean squares (never negative), a ballot ahead of
+// the chain has excluded a NaN (a wavefront that holds one takes the two-pass bit-pattern maximum, unchanged), and all 64 lanes are active.  IEEE mode stays on, so
+// every other fmax / fmin keeps its instructions.  Same values: still the general fast kernel's bits (profiles/wave_max_raw.md, tests/test_gpu_wave_max_raw.py).
 //
 // Its results are NOT bit-comparable with the oracle (every other kernel of the library is); north_star asks for 1e-6 relative on the states,
 // which the tests hold it to at tight tolerances; at the bench's full size it makes the step decisions of the exact kernel (every member's five counters equal,

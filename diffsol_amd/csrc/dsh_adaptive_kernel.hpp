@@ -154,11 +154,65 @@ __device__ __forceinline__ double uniform(double v) {
 // one-pass reduction (wave_max_nonneg_f64, dsh_device.hpp: the same bits, returned in scalar registers).  That reduction reads its result from lane 63
 // and lets rows without a DPP source read +0: every call site must be reached by ALL 64 lanes of the wavefront (here the shadow lanes of a ragged last
 // group keep executing the whole kernel and only their stores are masked), and the argument must not be negative.  Not a drop-in for group_norm elsewhere.
+// The LOCKFAST arm of k_bdf_adaptive takes group_norm_w_lock below instead (the same bits from fewer instructions); every other arm and kernel takes this one.
 template <bool WAVE>
 __device__ __forceinline__ double group_norm_w(double v) {
   if constexpr (WAVE) return wave_max_nonneg_f64(v);
   else return v;
 }
+
+// FAST, lock-step groups with the default options (LOCKFAST in k_bdf_adaptive): the wavefront maxima without the maximum that only quiets a NaN
+// (profiles/wave_max_raw.md).  dpp_max_f64 (dsh_device.hpp) is __builtin_fmax on a value put together from two v_mov_b32_dpp.  The kernel runs in IEEE mode, where
+// v_max_f64 of a signalling NaN is not the maxnum the builtin promises, and the compiler cannot see through the bit cast that the moved value is none: it puts
+// v_max_f64 x, x, x in front of every stage's maximum (and one more in front of the first stage, for the argument).  Each of them is issued, and each is a link of the
+// reduction's serial chain: s_nop, two DPP moves, the quieting maximum, the maximum.  The stage below names the instruction itself, so a stage is two v_mov_b32_dpp
+// and ONE v_max_f64; the asm is not volatile and has no side effect, the scheduler moves it like any other instruction, and the s_nop the hardware needs between a
+// VALU write and a DPP read of the same register is still placed by the compiler.
+// EXACT UNDER THESE CONDITIONS, which the callers establish: all 64 lanes active (the contract of group_norm_w), the argument NOT NEGATIVE (+0, denormal, normal,
+// +inf: FP64 denormals are on in every build of this library, v_max_f64 returns them unchanged) and NO NaN in any lane.  The quieting maximum is then the identity,
+// bit for bit, and v_max_f64 of two such values is the larger bit pattern: the result has the bits of wave_max_nonneg_f64.  A lane without a DPP source reads +0
+// (bound_ctrl), as there.  A NaN is excluded by the caller's ballot (wave_any_nan) ahead of the chain: a wavefront that holds one takes the two-pass bit-pattern
+// maximum (wave_max_u64), unchanged.  IEEE mode stays on for the kernel: every other fmax / fmin of the body keeps its instructions.
+// Only the LOCKFAST arm uses these; the general fast kernel, the exact translation unit, the per-member kernels and every run-time-compiled kernel keep
+// group_norm_w / wave_max_nonneg_f64 and their instructions.  DSH_RAW_WAVE_MAX=0: the parent's instructions here too.
+#ifndef DSH_RAW_WAVE_MAX
+#define DSH_RAW_WAVE_MAX 1
+#endif
+// Tried with it and dropped, neither faster than this alone (profiles/wave_max_raw.md): the order selection's two norms as one interleaved chain behind one
+// ballot, and predict_forward's q from D_1 instead of 1.0 * D_1.
+template <int CTRL>
+__device__ __forceinline__ double dpp_max_f64_raw(double v) {
+  const double m = __hiloint2double(__builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, true), __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, true));
+  double r;
+  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(v), "v"(m));
+  return r;
+}
+// wave_max_nonneg_f64_chain (dsh_device.hpp) with the stage above: the six stages and the read of lane 63, NO NaN test
+__device__ __forceinline__ double wave_max_nonneg_f64_chain_raw(double v) {
+  v = dpp_max_f64_raw<kDppQuadXor1>(v);
+  v = dpp_max_f64_raw<kDppQuadXor2>(v);
+  v = dpp_max_f64_raw<kDppRowHalfMirror>(v);
+  v = dpp_max_f64_raw<kDppRowMirror>(v);
+  v = dpp_max_f64_raw<kDppRowBcast15>(v);
+  v = dpp_max_f64_raw<kDppRowBcast31>(v);
+  return __longlong_as_double((long long)readlane_u64(d2u(v), 63));
+}
+// wave_max_nonneg_f64 with that chain; RAW = false is wave_max_nonneg_f64 itself
+template <bool RAW>
+__device__ __forceinline__ double wave_max_nonneg_f64_sel(double v) {
+  if constexpr (RAW) {
+    if (__builtin_expect(wave_any_nan(v), 0)) return __longlong_as_double((long long)wave_max_u64(d2u(v)));
+    return wave_max_nonneg_f64_chain_raw(v);
+  } else return wave_max_nonneg_f64(v);
+}
+template <bool RAW>
+__device__ __forceinline__ double wave_max_nonneg_f64_chain_sel(double v) {
+  if constexpr (RAW) return wave_max_nonneg_f64_chain_raw(v);
+  else return wave_max_nonneg_f64_chain(v);
+}
+// group_norm_w for the LOCKFAST arm (always WAVE)
+template <bool RAW>
+__device__ __forceinline__ double group_norm_w_lock(double v) { return wave_max_nonneg_f64_sel<RAW>(v); }
 
 // FAST only (dsh_adaptive_fast.hip): the two powers with a fixed exponent on the Newton chain, in place of the general pow (a call of some 220 vector
 // instructions, 150 of them FP64).  Both feed decisions only (eta * norm < tol, rate > 0.9, the divergence test), never a state, and both are within a few
@@ -217,10 +271,12 @@ __device__ __forceinline__ int ballot_decide_below(double v, double T) {
 // newton_first_threshold(tol, eta08), formed ahead of the solve (eta is known before the iteration starts).  `undecided` reports the cold path (tests/ballot_decide_check).
 // eta08 is positive or a NaN (eta is clamped from below before its power is taken); a NaN, zero or infinite eta08 gives a threshold that fails t_ok.
 __device__ __forceinline__ double newton_first_threshold(double tol, double eta08) { const double q = tol / eta08; return q * q; }
+// RAW: the cold path's maximum by wave_max_nonneg_f64_sel<true> (the LOCKFAST arm with DSH_RAW_WAVE_MAX); the same bits.
+template <bool RAW = false>
 __device__ __forceinline__ bool newton_first_converged(double dms, double thr2, double eta08, double tol, bool& undecided) {
   const int d = ballot_decide_below(dms, thr2);
   undecided = d == kBallotUndecided;
-  if (__builtin_expect(undecided, 0)) return eta08 * sqrt(wave_max_nonneg_f64(dms)) < tol;
+  if (__builtin_expect(undecided, 0)) return eta08 * sqrt(wave_max_nonneg_f64_sel<RAW>(dms)) < tol;
   return d == kBallotAllBelow;
 }
 // x^(1/k) for x positive, normal and finite: sqrt for k = 2, cbrt for k = 3 (the convergence rate of the third and fourth Newton iteration; the ratio is
@@ -336,6 +392,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DSH_ADAPTIVE
   constexpr bool kLit = DSH_ORDER_PATHS_LITERALS != 0;  // per-order bodies (with_order above): the order's coefficients as constants
   const AdaptiveConsts& C = *Cp;
   constexpr bool kPairPrio = LOCKFAST && DSH_PAIR_PRIO != 0;
+  constexpr bool kRawMax = LOCKFAST && DSH_RAW_WAVE_MAX != 0;                // its wavefront maxima by dpp_max_f64_raw (above)
   static_assert((DSH_PAIR_PRIO_PERIOD & (DSH_PAIR_PRIO_PERIOD - 1)) == 0 && DSH_PAIR_PRIO_PERIOD > 0, "DSH_PAIR_PRIO_PERIOD: a power of two");
   static_assert(DSH_PAIR_PRIO_HIGH >= 0 && DSH_PAIR_PRIO_HIGH < 2 * DSH_PAIR_PRIO_PERIOD, "DSH_PAIR_PRIO_HIGH: trips of the 2 x DSH_PAIR_PRIO_PERIOD");
   // the wavefront's role in the policy (DSH_PAIR_PRIO above): 0 = no policy in this launch, no s_setprio; 1 = a wavefront of the first round of the dispatch (the
@@ -944,7 +1001,7 @@ DSH_UNROLL_N
           eta = eta08;
           niter = 1;
           bool undecided;
-          if (newton_first_converged(dms1, thr2, eta08, tol, undecided)) solved = true;
+          if (newton_first_converged<kRawMax>(dms1, thr2, eta08, tol, undecided)) solved = true;
           else if (o.max_nonlinear_solver_iterations > 1) {
             // ---- iteration 2.  The first update's norm, which nothing has read so far, is reduced HERE, in the basic block of this iteration's residual and
             // substitution, of which it is independent.  As compiled the six stages follow the substitution, two instructions of the update and the weighted sum
@@ -953,12 +1010,17 @@ DSH_UNROLL_N
             // wave_max_nonneg_f64 does; the chain then runs for nothing and its result is dropped.
             double nan_nrm = 0.0;
             const bool nan1 = wave_any_nan(dms1);
-            if (__builtin_expect(nan1, 0)) nan_nrm = sqrt(wave_max_nonneg_f64(dms1));
+            if (__builtin_expect(nan1, 0)) {
+              // kRawMax: the two-pass maximum itself.  nan1 IS wave_max_nonneg_f64's own test, so that call takes this path and no other; named directly, its
+              // one-pass arm (never executed here, but compiled) is gone.
+              if constexpr (kRawMax) nan_nrm = sqrt(__longlong_as_double((long long)wave_max_u64(d2u(dms1))));
+              else nan_nrm = sqrt(wave_max_nonneg_f64(dms1));
+            }
             double nrm1 = 0.0;
             double dms2;
-            if (newton_update(dms2, [&]() __attribute__((always_inline)) { nrm1 = sqrt(wave_max_nonneg_f64_chain(dms1)); })) {
+            if (newton_update(dms2, [&]() __attribute__((always_inline)) { nrm1 = sqrt(wave_max_nonneg_f64_chain_sel<kRawMax>(dms1)); })) {
               const double old_nrm = nan1 ? nan_nrm : nrm1;
-              double norm = sqrt(group_norm_w<WAVE>(dms2));
+              double norm = sqrt(group_norm_w_lock<kRawMax>(dms2));
               niter = 2;
               int r = rate_test(norm, old_nrm);
               if (r == 1) solved = true;
@@ -966,7 +1028,7 @@ DSH_UNROLL_N
               for (int it = 2; r == 0 && it < o.max_nonlinear_solver_iterations; ++it) {
                 double dms;
                 if (!newton_update(dms, []() {})) break;
-                norm = sqrt(group_norm_w<WAVE>(dms));
+                norm = sqrt(group_norm_w_lock<kRawMax>(dms));
                 niter += 1;
                 r = rate_test(norm, old_nrm);
                 if (r == 1) solved = true;
@@ -1141,7 +1203,8 @@ DSH_UNROLL_N
       // WAVE: the error test, the step-size factor with its clamps, the order-selection norms and the chosen order, h, t and the stop-time tests are scalar
       // branches for the same reason as the convergence test: group_norm_w returns in scalar registers, and h (initial_step_size) and the error-test
       // failure's pi_controller_raw, which end in the rpow call, go through uniform<WAVE>().  Keep it so when adding an input to any of them.
-      error_norm = fmax(0.0, group_norm_w<WAVE>(wms_y(ydelta)) * sEc2[order - 1]);
+      if constexpr (kRawMax) error_norm = fmax(0.0, group_norm_w_lock<true>(wms_y(ydelta)) * sEc2[order - 1]);
+      else error_norm = fmax(0.0, group_norm_w<WAVE>(wms_y(ydelta)) * sEc2[order - 1]);
       if constexpr (SENS) {
         if (C.sens_error_control)  // bdf.rs:844-858 — error_const2[order], not [order - 1]
           for (int j = 0; j < NP; ++j) error_norm = fmax(error_norm, group_norm_w<WAVE>(wms<N>(s_delta[j], s_cur[j], s_atol, C.sens_rtol)) * sEc2[order]);
@@ -1272,8 +1335,8 @@ DSH_UNROLL_N
           constexpr int Q = decltype(qc)::value;
           constexpr BdfTables T = bdf_new_tables();
           error_m_norm = inf; error_p_norm = inf;
-          if constexpr (Q > 1) error_m_norm = group_norm_w<WAVE>(wms_y(D[Q])) * (kLit ? T.ec2[Q - 1] : sEc2[Q - 1]);
-          if constexpr (Q < kMaxOrder) error_p_norm = group_norm_w<WAVE>(wms_y(D[Q + 2])) * (kLit ? T.ec2[Q < kMaxOrder ? Q + 1 : Q] : sEc2[Q < kMaxOrder ? Q + 1 : Q]);
+          if constexpr (Q > 1) error_m_norm = group_norm_w_lock<kRawMax>(wms_y(D[Q])) * (kLit ? T.ec2[Q - 1] : sEc2[Q - 1]);
+          if constexpr (Q < kMaxOrder) error_p_norm = group_norm_w_lock<kRawMax>(wms_y(D[Q + 2])) * (kLit ? T.ec2[Q < kMaxOrder ? Q + 1 : Q] : sEc2[Q < kMaxOrder ? Q + 1 : Q]);
         });
       } else {
       if constexpr (WAVE) {

@@ -104,6 +104,10 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
 constexpr int kDppRowBcast15 = 0x142, kDppRowBcast31 = 0x143;
 // a lane without a source (the row broadcasts: row 0, rows 0 and 1) reads +0 (bound_ctrl), the identity of this maximum; the rows a broadcast reaches
 // beyond the two named above only see values of the same wavefront again.  No previous value of the destination is kept, so no register is copied first.
+// As compiled, a stage is s_nop, two v_mov_b32_dpp, v_max_f64 x, x, x and the maximum: the kernels run in IEEE mode, __builtin_fmax is maxnum, and the compiler
+// quiets the moved value (it cannot see through the bit cast that it is no signalling NaN), and the argument of the first stage as well.  Every kernel that includes
+// this header keeps that stage.  The one exception is the lock-step fast BDF with the default options, which has a stage of its own without the quieting maximum next
+// to its group_norm_w (dpp_max_f64_raw, dsh_adaptive_kernel.hpp: exact for non-negative values without a NaN, all 64 lanes active; profiles/wave_max_raw.md).
 template <int CTRL>
 __device__ __forceinline__ double dpp_max_f64(double v) {
   return __builtin_fmax(v, __hiloint2double(__builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, true), __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, true)));

@@ -78,9 +78,36 @@ DSH_UNROLL_N
   }
 }
 
-// The two halves of interpolate_inplace (runge_kutta.rs:968-981 interpolate_beta_function, :962-966 interpolate_from_diff) apart, for the kernel with sensitivities:
-// the beta function of a save point is computed once and applied to the state and to every sensitivity (interpolate_sens_inplace, :1237-1309).  The operations and
-// their order are those of the kernel's `interpolate`.
+// The gemv that every stage point, error vector and dense output is (nalgebra's order, as the checkers restate it): ret = d[:, 0..n) c accumulated from column 0
+// upward, every term 1.0 * d[j][r] * c[j]; with a base vector ret = base + d[:, 0..n) c, the base added in the first term.  `c` is anything indexable: a tableau row
+// (kTsitD: error_norm, runge_kutta.rs:783-822; kTsitB: the accepted g, :900-909), the beta function of a save point (interpolate_from_diff, :962-966), or a(i, .) of
+// stage i (ErkRowA: do_stage, :537-607).
+struct ErkRowA {
+  int i;
+  __device__ constexpr double operator[](int j) const { return erk_a(i, j); }
+};
+template <int R, class Row>
+__device__ __forceinline__ void erk_fold(const Row& c, int n, const double (&d)[kErkStages][R], double (&ret)[R]) {
+DSH_UNROLL_N
+  for (int r = 0; r < R; ++r) {
+    double acc = 1.0 * d[0][r] * c[0];
+#pragma unroll
+    for (int j = 1; j < n; ++j) acc = 1.0 * d[j][r] * c[j] + acc;
+    ret[r] = acc;
+  }
+}
+template <int R, class Row>
+__device__ __forceinline__ void erk_fold(const Row& c, int n, const double (&base)[R], const double (&d)[kErkStages][R], double (&ret)[R]) {
+DSH_UNROLL_N
+  for (int r = 0; r < R; ++r) {
+    double acc = 1.0 * d[0][r] * c[0] + 1.0 * base[r];
+#pragma unroll
+    for (int j = 1; j < n; ++j) acc = 1.0 * d[j][r] * c[j] + acc;
+    ret[r] = acc;
+  }
+}
+// interpolate_beta_function (runge_kutta.rs:968-981) inside the last step [old_t, t].  Apart from its application, because the kernel with sensitivities computes it
+// once per save point and applies it to the state and to every sensitivity (interpolate_sens_inplace, :1237-1309).
 __device__ __forceinline__ void erk_beta_function(double t, double old_t, double tt, double (&bf)[kErkStages]) {
   const double dt = t - old_t;
   const double theta = dt == 0.0 ? 1.0 : (tt - old_t) / dt;
@@ -96,15 +123,30 @@ __device__ __forceinline__ void erk_beta_function(double t, double old_t, double
     bf[i] = acc;
   }
 }
-template <int N>
-__device__ __forceinline__ void erk_from_diff(const double (&bf)[kErkStages], const double (&y0)[N], const double (&df)[kErkStages][N], double (&ret)[N]) {
+// interpolate_inplace (runge_kutta.rs:1080-1127; for g interpolate_out_inplace, :1185-1235): the beta function of tt applied to (base, d) of the last step
+template <int R>
+__device__ __forceinline__ void erk_interpolate(double t, double old_t, double tt, const double (&base)[R], const double (&d)[kErkStages][R], double (&ret)[R]) {
+  double bf[kErkStages];
+  erk_beta_function(t, old_t, tt, bf);
+  erk_fold(bf, kErkStages, base, d, ret);
+}
+// The two output layouts, each address written once: column `col` of y_out [col][R][nb] (R rows: the states, or the integrated outputs) and the block of parameter j
+// in column `col` of sens_out [col][np][N][nb].  The lanes that shadow a member store nothing.
+template <int R>
+__device__ __forceinline__ void erk_write_col(double* __restrict__ y_out, int64_t nb, int64_t b, bool active, int col, const double (&v)[R]) {
 DSH_UNROLL_N
-  for (int i = 0; i < N; ++i) {
-    double acc = 1.0 * df[0][i] * bf[0] + 1.0 * y0[i];
-#pragma unroll
-    for (int j = 1; j < kErkStages; ++j) acc = 1.0 * df[j][i] * bf[j] + acc;
-    ret[i] = acc;
-  }
+  for (int i = 0; i < R; ++i) if (active) y_out[((int64_t)col * R + i) * nb + b] = v[i];
+}
+template <int N>
+__device__ __forceinline__ void erk_write_sens(double* __restrict__ sens_out, int64_t nb, int64_t b, bool active, int col, int np, int j, const double (&v)[N]) {
+DSH_UNROLL_N
+  for (int i = 0; i < N; ++i) if (active) sens_out[(((int64_t)col * np + j) * N + i) * nb + b] = v[i];
+}
+// what a column of y_out holds: g with integrated outputs, y without
+template <bool INTOUT, class G, class Y>
+__device__ __forceinline__ auto& erk_column(G& g, Y& y) {
+  if constexpr (INTOUT) return g;
+  else return y;
 }
 
 // One lane per member: ExplicitRk::step (explicit_rk.rs:196-243) over the Rk core (runge_kutta.rs), root finding on the dense output, tstop, solve_dense /
@@ -217,63 +259,26 @@ DSH_UNROLL_N
     }
     return 0;
   };
-  // interpolate_inplace (runge_kutta.rs:1080-1127) inside the last step [old_t, t]: interpolate_beta_function (:968-981) + interpolate_from_diff (:962-966)
-  auto interpolate = [&](double tt, double (&ret)[N]) __attribute__((always_inline)) {
-    const double dt = t - old_t;
-    const double theta = dt == 0.0 ? 1.0 : (tt - old_t) / dt;
-    double thetav[kErkPoly];
-    thetav[0] = theta;
-#pragma unroll
-    for (int q = 1; q < kErkPoly; ++q) thetav[q] = theta * thetav[q - 1];
-    double bf[S];
-#pragma unroll
-    for (int i = 0; i < S; ++i) {
-      double acc = 1.0 * kTsitBeta[0][i] * thetav[0];
-#pragma unroll
-      for (int q = 1; q < kErkPoly; ++q) acc = 1.0 * kTsitBeta[q][i] * thetav[q] + acc;
-      bf[i] = acc;
-    }
-DSH_UNROLL_N
-    for (int i = 0; i < N; ++i) {
-      double acc = 1.0 * diff[0][i] * bf[0] + 1.0 * old_y[i];
-#pragma unroll
-      for (int j = 1; j < S; ++j) acc = 1.0 * diff[j][i] * bf[j] + acc;
-      ret[i] = acc;
-    }
-  };
+  auto interpolate = [&](double tt, double (&ret)[N]) __attribute__((always_inline)) { erk_interpolate(t, old_t, tt, old_y, diff, ret); };  // the root finder's
+  // What a column of y_out holds: NROW rows of g with INTOUT, of y without; (col_old, col_diff) is what its dense output interpolates
+  constexpr int NROW = INTOUT ? NO : N;
+  const double (&col_now)[NROW] = erk_column<INTOUT>(g, y);
+  const double (&col_old)[NROW] = erk_column<INTOUT>(old_g, old_y);
+  const double (&col_diff)[S][NROW] = erk_column<INTOUT>(gdiff, diff);
+  auto column_at = [&](double tt, double (&ret)[NROW]) __attribute__((always_inline)) { erk_interpolate(t, old_t, tt, col_old, col_diff, ret); };
 
   int col = 0;
   double t_root = 0.0;
   int root_idx = -1;
   const bool steps_mode = !SENS && T.steps_cap > 0;  // every accepted step out (ErkConsts::steps_cap)
-  auto steps_write = [&](double tw, const double (&yw)[N]) __attribute__((always_inline)) {
-    if (col < T.steps_cap && active) {
-      T.steps_t_out[(int64_t)col * nb + b] = tw;
-DSH_UNROLL_N
-      for (int i = 0; i < N; ++i) y_out[((int64_t)col * N + i) * nb + b] = yw[i];
+  auto steps_write = [&](double tw, const double (&v)[NROW]) __attribute__((always_inline)) {
+    if (col < T.steps_cap) {
+      if (active) T.steps_t_out[(int64_t)col * nb + b] = tw;
+      erk_write_col(y_out, nb, b, active, col, v);
     }
     col++;
   };
-  // the same two writers with g in the column (INTOUT): NO rows
-  auto steps_write_g = [&](double tw, const double (&gw)[NO]) __attribute__((always_inline)) {
-    if (col < T.steps_cap && active) {
-      T.steps_t_out[(int64_t)col * nb + b] = tw;
-#pragma unroll
-      for (int k = 0; k < NO; ++k) y_out[((int64_t)col * NO + k) * nb + b] = gw[k];
-    }
-    col++;
-  };
-  // interpolate_out_inplace (runge_kutta.rs:1185-1235): the beta function of the save point applied to (old_g, gdiff)
-  auto interpolate_g = [&](double tt, double (&ret)[NO]) __attribute__((always_inline)) {
-    if constexpr (INTOUT) {
-      double bf[S];
-      erk_beta_function(t, old_t, tt, bf);
-      erk_from_diff<NO>(bf, old_g, gdiff, ret);
-    }
-  };
-  if constexpr (INTOUT) { if (steps_mode) steps_write_g(t, g); }  // write_out before the first step: state.g = 0
-  else
-  if (steps_mode) steps_write(t, y);  // write_out before the first step (method.rs:900)
+  if (steps_mode) steps_write(t, col_now);  // write_out before the first step (method.rs:900); state.g = 0
   {  // set_stop_time (runge_kutta.rs:436-444); t_eval[0] >= t0 is checked on the host
     const int r = handle_tstop();
     if (r == 1) status = kRsStopTimeAtCurrentTime;
@@ -307,13 +312,7 @@ DSH_UNROLL_N
       for (int i = 1; i < S; ++i) {
         // do_stage (runge_kutta.rs:537-566): old_state.y = y + diff[:, 0..i] a_row_i (nalgebra gemv order), diff[:, i] = h f(old_state.y, t + c_i h)
         const double ts = t + kTsitC[i] * hh;
-DSH_UNROLL_N
-        for (int r = 0; r < N; ++r) {
-          double acc = 1.0 * diff[0][r] * erk_a(i, 0) + 1.0 * y[r];
-#pragma unroll
-          for (int j = 1; j < i; ++j) acc = 1.0 * diff[j][r] * erk_a(i, j) + acc;
-          sy[r] = acc;
-        }
+        erk_fold(ErkRowA{i}, i, y, diff, sy);
         Mdl::rhs(ts, sy, p, sdy);
 DSH_UNROLL_N
         for (int r = 0; r < N; ++r) diff[i][r] = hh * sdy[r];
@@ -328,13 +327,7 @@ DSH_UNROLL_N
             double ev[NP], jm[N], dfdp[N];
 #pragma unroll
             for (int k = 0; k < NP; ++k) ev[k] = k == j ? 1.0 : 0.0;
-DSH_UNROLL_N
-            for (int r = 0; r < N; ++r) {
-              double acc = 1.0 * sdiff[j][0][r] * erk_a(i, 0) + 1.0 * s[j][r];
-#pragma unroll
-              for (int q = 1; q < i; ++q) acc = 1.0 * sdiff[j][q][r] * erk_a(i, q) + acc;
-              ss[j][r] = acc;
-            }
+            erk_fold(ErkRowA{i}, i, s[j], sdiff[j], ss[j]);
             Mdl::sens_mul(ts, sy, p, ev, dfdp);
             Mdl::jac_mul(ts, sy, p, ss[j], jm);
 DSH_UNROLL_N
@@ -344,24 +337,12 @@ DSH_UNROLL_N
       }
       // error_norm (runge_kutta.rs:783-800): diff d, no linear solve
       double err[N];
-DSH_UNROLL_N
-      for (int r = 0; r < N; ++r) {
-        double acc = 1.0 * diff[0][r] * kTsitD[0];
-#pragma unroll
-        for (int j = 1; j < S; ++j) acc = 1.0 * diff[j][r] * kTsitD[j] + acc;
-        err[r] = acc;
-      }
+      erk_fold(kTsitD, S, diff, err);
       error_norm = fmax(0.0, group_norm<WAVE>(wms<N>(err, y, atol, rtol)));
       if constexpr (INTOUT) {  // :802-810: gdiff d against state.g (the g at the start of the step) with the output tolerances, after the states' norm
         if (T.out_error_control) {
           double oerr[NO];
-#pragma unroll
-          for (int k = 0; k < NO; ++k) {
-            double acc = 1.0 * gdiff[0][k] * kTsitD[0];
-#pragma unroll
-            for (int q = 1; q < S; ++q) acc = 1.0 * gdiff[q][k] * kTsitD[q] + acc;
-            oerr[k] = acc;
-          }
+          erk_fold(kTsitD, S, gdiff, oerr);
           error_norm = fmax(error_norm, group_norm<WAVE>(wms<NO>(oerr, g, o_atol, T.out_rtol)));
         }
       }
@@ -370,13 +351,7 @@ DSH_UNROLL_N
 #pragma unroll
           for (int j = 0; j < NP; ++j) {
             double serr[N];
-DSH_UNROLL_N
-            for (int r = 0; r < N; ++r) {
-              double acc = 1.0 * sdiff[j][0][r] * kTsitD[0];
-#pragma unroll
-              for (int q = 1; q < S; ++q) acc = 1.0 * sdiff[j][q][r] * kTsitD[q] + acc;
-              serr[r] = acc;
-            }
+            erk_fold(kTsitD, S, sdiff[j], serr);
             error_norm = fmax(error_norm, group_norm<WAVE>(wms<N>(serr, s[j], s_atol, T.sens_rtol)));
           }
         }
@@ -401,14 +376,10 @@ DSH_UNROLL_N
     prev_err = error_norm; has_prev_err = true;
     // ---- step_accepted(h, h * factor, rescale_dy = false) (runge_kutta.rs:894-960): old_state <- (last stage point, its derivative, t + h, new_h); swap
     {
-      if constexpr (INTOUT) {  // :900-909: old_state.g = state.g + gdiff b, then the swap (which takes the last stage's dg along)
+      if constexpr (INTOUT) {  // :900-909: old_state.g = state.g + gdiff b (all seven terms: b, not row 6 of a), then the swap (which takes the last stage's dg along)
+        erk_fold(kTsitB, S, g, gdiff, old_g);
 #pragma unroll
-        for (int k = 0; k < NO; ++k) {
-          double acc = 1.0 * gdiff[0][k] * kTsitB[0] + 1.0 * g[k];
-#pragma unroll
-          for (int q = 1; q < S; ++q) acc = 1.0 * gdiff[q][k] * kTsitB[q] + acc;
-          old_g[k] = g[k]; g[k] = acc; dg[k] = sdg[k];
-        }
+        for (int k = 0; k < NO; ++k) { const double gk = g[k]; g[k] = old_g[k]; old_g[k] = gk; dg[k] = sdg[k]; }
       }
 DSH_UNROLL_N
       for (int r = 0; r < N; ++r) { old_y[r] = y[r]; y[r] = sy[r]; dy[r] = sdy[r]; }
@@ -438,55 +409,35 @@ DSH_UNROLL_N
     // ================================================================ solve_dense (method.rs:467-520) / solve (:881-961)
     const double upto = reason == 3 ? t_root : t;
     if (steps_mode) {  // InternalTimestep / TstopReached -> write_out: state.y (state.g with INTOUT); a root is written below, at the root
-      if (reason != 3) { if constexpr (INTOUT) steps_write_g(t, g); else steps_write(t, y); }
-    } else if constexpr (INTOUT) {
+      if (reason != 3) steps_write(t, col_now);
+    } else {
       while (col < C.n_eval && t_eval[col] <= upto) {
-        double gv[NO];
-        interpolate_g(t_eval[col], gv);
+        double v[NROW];
+        if constexpr (!SENS) {
+          column_at(t_eval[col], v);
+          erk_write_col(y_out, nb, b, active, col, v);
+        } else {  // interpolate_sens_inplace (:1237-1309): one beta function for the state, old_state.s_j and sdiff_j.  The state's column is written first, and in
+          // this branch: after the sensitivities' the compiler gives this kernel 16 vector registers more; with bf in the loop's scope the plain kernel's schedule changes
+          double bf[S];
+          erk_beta_function(t, old_t, t_eval[col], bf);
+          erk_fold(bf, S, old_y, diff, v);
+          erk_write_col(y_out, nb, b, active, col, v);
 #pragma unroll
-        for (int k = 0; k < NO; ++k) if (active) y_out[((int64_t)col * NO + k) * nb + b] = gv[k];
+          for (int j = 0; j < NP; ++j) {
+            double sv[N];
+            erk_fold(bf, S, old_s[j], sdiff[j], sv);
+            erk_write_sens(T.sens_out, nb, b, active, col, NP, j, sv);
+          }
+        }
         col++;
       }
-    } else
-    while (col < C.n_eval && t_eval[col] <= upto) {
-      double yv[N];
-      if constexpr (!SENS) interpolate(t_eval[col], yv);
-      else {  // interpolate_sens_inplace (:1237-1309): one beta function for the state, old_state.s_j and sdiff_j
-        double bf[S];
-        erk_beta_function(t, old_t, t_eval[col], bf);
-        erk_from_diff<N>(bf, old_y, diff, yv);
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-          double sv[N];
-          erk_from_diff<N>(bf, old_s[j], sdiff[j], sv);
-DSH_UNROLL_N
-          for (int i = 0; i < N; ++i) if (active) T.sens_out[(((int64_t)col * NP + j) * N + i) * nb + b] = sv[i];
-        }
-      }
-DSH_UNROLL_N
-      for (int i = 0; i < N; ++i) if (active) y_out[((int64_t)col * N + i) * nb + b] = yv[i];
-      col++;
     }
-    if (reason == 3 && INTOUT) {  // state_mut_back(t_root, integrate_out) (:396-434): g at the root goes where the state goes
-      if constexpr (INTOUT) {
-        double gv[NO];
-        interpolate_g(t_root, gv);
-        if (steps_mode) steps_write_g(t_root, gv);
-        else if (col < C.n_eval) {
-#pragma unroll
-          for (int k = 0; k < NO; ++k) if (active) y_out[((int64_t)col * NO + k) * nb + b] = gv[k];
-          col++;
-        }
-      }
-      done = true;
-    } else
-    if (reason == 3) {  // state_mut_back(t_root): the column after the drained ones holds the state at the root
-      double yv[N];
-      interpolate(t_root, yv);
-      if (steps_mode) steps_write(t_root, yv);
+    if (reason == 3) {  // state_mut_back(t_root) (:396-434): the column after the drained ones holds the state (g with INTOUT) at the root
+      double v[NROW];
+      column_at(t_root, v);
+      if (steps_mode) steps_write(t_root, v);
       else if (col < C.n_eval) {
-DSH_UNROLL_N
-        for (int i = 0; i < N; ++i) if (active) y_out[((int64_t)col * N + i) * nb + b] = yv[i];
+        erk_write_col(y_out, nb, b, active, col, v);
         col++;
       }
       done = true;
@@ -495,19 +446,16 @@ DSH_UNROLL_N
   }
   if (active) {
     if (ncols_out != nullptr) ncols_out[b] = col;
-    if (!steps_mode)
-    for (; col < C.n_eval; ++col) {  // columns that were never reached (root stop or error exit): NaN
-      if constexpr (INTOUT) {
-#pragma unroll
-        for (int k = 0; k < NO; ++k) y_out[((int64_t)col * NO + k) * nb + b] = __builtin_nan("");
-      } else
+    if (!steps_mode) {  // columns that were never reached (root stop or error exit): NaN
+      double nan_col[NROW];
 DSH_UNROLL_N
-      for (int i = 0; i < N; ++i) y_out[((int64_t)col * N + i) * nb + b] = __builtin_nan("");
-      if constexpr (SENS) {
+      for (int i = 0; i < NROW; ++i) nan_col[i] = __builtin_nan("");
+      for (; col < C.n_eval; ++col) {
+        erk_write_col(y_out, nb, b, active, col, nan_col);
+        if constexpr (SENS) {  // NROW is N here
 #pragma unroll
-        for (int j = 0; j < NP; ++j)
-DSH_UNROLL_N
-          for (int i = 0; i < N; ++i) T.sens_out[(((int64_t)col * NP + j) * N + i) * nb + b] = __builtin_nan("");
+          for (int j = 0; j < NP; ++j) erk_write_sens(T.sens_out, nb, b, active, col, NP, j, nan_col);
+        }
       }
     }
     if (status_out != nullptr) status_out[b] = status;

@@ -26,6 +26,7 @@ struct dshs_solver {
   bool fused = false;
   bool kernel_timing = false;
   int method = 0;
+  int64_t max_steps = 0;  // dshs_options.max_steps: the step cap of the device-resident solves (0: the device default)
   // OdeBuilder::integrate_out (dshs_set_integrate_out): the device-resident Tsit45 solves return g = integral of out(y, t) in place of the states
   bool integrate_out = false;
   double out_rtol = 0.0;
@@ -315,6 +316,7 @@ dsh_adaptive_options adaptive_options_of(const dshs_solver* s, int group, int de
   o.ic_armijo_constant = ic.armijo_constant;
   o.group = group;
   o.deterministic_pow = deterministic_pow;
+  if (s->max_steps > 0) o.max_steps = s->max_steps;
   return o;
 }
 
@@ -565,6 +567,7 @@ void dshs_default_options(dshs_options* o) {
   o->ic_max_newton_iterations = 10;
   o->ic_step_reduction_factor = 0.5;
   o->ic_armijo_constant = 1e-4;
+  o->max_steps = 0;
 }
 
 int dshs_create(int device, void* stream, int model, int64_t model_size, int64_t nbatch, const double* params, int64_t nparams_total, double rtol,
@@ -609,6 +612,7 @@ int dshs_create_sens(int device, void* stream, int model, int64_t model_size, in
     }
     s->problem = builder.build_model(model, model_size, p);
     s->method = method;
+    s->max_steps = o.max_steps;
     s->make_solver();
     check(dsh_ctx_flush(s->ctx.raw()), "dsh_ctx_flush");
     *out = s.release();

@@ -68,6 +68,8 @@ class Solver:
         o.use_fused_kernels = 1 if fused else 0
         o.block_threads = int(block_threads)
         for k, v in (options or {}).items():
+            if k not in dict(DshsOptions._fields_):  # setattr would keep an unknown name as a Python attribute and the option would be ignored
+                raise DiffsolHipError(-1, f"Solver: unknown option {k!r}; dshs_options has {', '.join(n for n, _ in DshsOptions._fields_)}")
             setattr(o, k, v)
         h = vp()
         if sens:  # problem.bdf_sens() / tr_bdf2_sens() / esdirk34_sens() / tsit45_sens(): forward sensitivities integrated alongside (sens_atol None: not part of the error control)

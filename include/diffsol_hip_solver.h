@@ -56,6 +56,8 @@ typedef struct {
   int ic_max_newton_iterations;        /* 10 */
   double ic_step_reduction_factor;     /* 0.5 */
   double ic_armijo_constant;           /* 1e-4 */
+  int64_t max_steps;                   /* 0 = default (10 000 000): dsh_adaptive_options.max_steps of the device-resident solves (dshs_solve_dense_adaptive and the
+                                          entries over it, dshs_solve_adaptive) — a member that needs more step() calls ends with status 99 */
 } dshs_options;
 
 const char* dshs_last_error(void);

@@ -38,7 +38,7 @@ def lib():
         L.erko_model_nout.argtypes = [C.c_int, C.c_int]
         L.erko_solve_to_points.argtypes = [C.c_int, C.c_int, _dp, C.c_int, C.c_double, _dp, C.c_double, C.c_double, C.c_int, C.c_double, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _lp]
         L.erko_solve_ensemble.argtypes = [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, _dp, C.c_int, _dp,
-                                          C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _lp, _ip, _dp, _ip, _ip, _lp]
+                                          C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _lp, _ip, _dp, _ip, _ip, _lp, _dp]
         _lib = L
     return _lib
 
@@ -94,9 +94,9 @@ def solve_to_points(model, p, t_points, *, model_size=0, rtol=1e-6, atol=(1e-6,)
 
 
 def solve_ensemble(model, p, t_eval, *, model_size=0, rtol=1e-6, atol=(1e-6,), t0=0.0, h0=1.0, group=1, nthreads=8, steps_cap=0, integrate_out=True, out_rtol=1e-6,
-                   out_atol=None):
+                   out_atol=None, options=None):
     """solve_dense (steps_cap = 0; t_eval the save points) or solve (steps_cap > 0; t_eval = [t_final]) per member (group 1) or per lock-step group of `group`
-    members, with the outputs integrated.  atol: [n] / scalar, or [nsys, n] per member.  Returns dict(y [nsys, cols, n] (the states), g [nsys, cols, nout] (None without
+    members, with the outputs integrated.  atol: [n] / scalar, or [nsys, n] per member.  options: see erk_ref.options_array.  Returns dict(y [nsys, cols, n] (the states), g [nsys, cols, nout] (None without
     integrate_out), t [nsys, cols] (steps only), stats [nsys, 5], status, t_root, root_idx, ncols, rhs_calls, failed)."""
     p = np.ascontiguousarray(p, dtype=np.float64)
     nsys, np_ = p.shape
@@ -115,7 +115,8 @@ def solve_ensemble(model, p, t_eval, *, model_size=0, rtol=1e-6, atol=(1e-6,), t
     calls = np.zeros(nsys, dtype=np.int64)
     status, ridx, ncols = (np.zeros(nsys, dtype=np.int32) for _ in range(3))
     troot = np.full(nsys, np.nan)
+    o_a, o_p = erk_ref.options_array(options)
     failed = lib().erko_solve_ensemble(model, model_size, nsys, p.ctypes.data_as(_dp), np_, rtol, a_p, rows, t0, h0, 1 if integrate_out else 0, out_rtol, oa_p, noa, te_p,
                                        te.size, nthreads, group, steps_cap, y.ctypes.data_as(_dp), g.ctypes.data_as(_dp), t.ctypes.data_as(_dp), stats.ctypes.data_as(_lp),
-                                       status.ctypes.data_as(_ip), troot.ctypes.data_as(_dp), ridx.ctypes.data_as(_ip), ncols.ctypes.data_as(_ip), calls.ctypes.data_as(_lp))
+                                       status.ctypes.data_as(_ip), troot.ctypes.data_as(_dp), ridx.ctypes.data_as(_ip), ncols.ctypes.data_as(_ip), calls.ctypes.data_as(_lp), o_p)
     return dict(y=y, g=(g if integrate_out else None), t=t, stats=stats, status=status, t_root=troot, root_idx=ridx, ncols=ncols, rhs_calls=calls, failed=int(failed))

@@ -170,10 +170,12 @@ int erko_solve_to_points(int model_id, int model_size, const double* p, int np, 
 // solve_dense / solve for an ensemble, as erk_solve_ensemble of the plain checker (group, steps_cap, atol rows, the per-member arrays), with integrate_out: y_out holds
 // the states as there, g_out [nsys][width][nout] the integrated outputs in the same columns (written only with integrate_out; at a root g interpolated at the root,
 // columns never reached NaN, the column before the first step zero).  nout_atol = 0: the outputs stay out of the error test; 1: one out_atol; nout: one each.
-// calls_out [nsys]: right-hand sides of the member's problem.  Returns the number of failed members.
+// calls_out [nsys]: right-hand sides of the member's problem.  options: as erk_solve_ensemble's.  Returns the number of failed members.
 int erko_solve_ensemble(int model_id, int model_size, int nsys, const double* p, int np, double rtol, const double* atol, int natol_rows, double t0, double h0,
                         int integrate_out, double out_rtol, const double* out_atol, int nout_atol, const double* t_eval, int nt, int nthreads, int group, int steps_cap,
-                        double* y_out, double* g_out, double* t_out, long* stats_out, int* status_out, double* root_t_out, int* root_idx_out, int* ncols_out, long* calls_out) {
+                        double* y_out, double* g_out, double* t_out, long* stats_out, int* status_out, double* root_t_out, int* root_idx_out, int* ncols_out, long* calls_out,
+                        const double* options) {
+  const SolveOptions so(options);
   if (group < 1) group = 1;
   if (nthreads < 1) nthreads = 1;
   const int ngroups = (nsys + group - 1) / group;
@@ -183,7 +185,7 @@ int erko_solve_ensemble(int model_id, int model_size, int nsys, const double* p,
   auto work = [&](int tid) {
     for (int gi = tid; gi < ngroups; gi += nthreads) {
       const int s0 = gi * group, cnt = std::min(group, nsys - s0);
-      auto pr = make_problem(model_id, model_size, cnt, p + (size_t)s0 * np, np, rtol, natol_rows == 1 ? atol : atol + (size_t)s0 * n_model, natol_rows, t0, h0);
+      auto pr = make_problem(model_id, model_size, cnt, p + (size_t)s0 * np, np, rtol, natol_rows == 1 ? atol : atol + (size_t)s0 * n_model, natol_rows, t0, h0, so);
       const int n = pr->n();
       const int width = steps_cap > 0 ? steps_cap : nt;
       ExplicitRkOut sv(pr.get(), tsit45(), integrate_out != 0, out_rtol, out_atol, nout_atol);
@@ -207,7 +209,10 @@ int erko_solve_ensemble(int model_id, int model_size, int nsys, const double* p,
         if (steps_cap > 0) steps_write(sv.t(), sv.y(), io ? &sv.g : nullptr);
         err = sv.set_stop_time(t_eval[nt - 1]);
       }
+      StepGuard cap(so);
+      bool capped = false;
       while (err == OdeErr::Ok) {
+        if (!cap.next()) { capped = true; break; }
         StopReason r;
         err = sv.step(r);
         if (err != OdeErr::Ok) break;
@@ -238,7 +243,7 @@ int erko_solve_ensemble(int model_id, int model_size, int nsys, const double* p,
             for (int i = 0; i < n; ++i) y_out[((size_t)m * nt + c2) * n + i] = nan;
             if (io) for (int i = 0; i < no; ++i) g_out[((size_t)m * nt + c2) * no + i] = nan;
           }
-        if (status_out) status_out[m] = status_of(err);
+        if (status_out) status_out[m] = capped ? kStatusMaxStepsExceeded : status_of(err);
         if (root_t_out) root_t_out[m] = rooted ? sv.root_time : nan;
         if (root_idx_out) root_idx_out[m] = rooted ? sv.root_index : -1;
         if (stats_out) {
@@ -247,7 +252,7 @@ int erko_solve_ensemble(int model_id, int model_size, int nsys, const double* p,
         }
         if (calls_out) calls_out[m] = pr->eqn->rhs_stats.calls;
       }
-      if (err != OdeErr::Ok) failed_per_thread[(size_t)tid] += cnt;
+      if (err != OdeErr::Ok || capped) failed_per_thread[(size_t)tid] += cnt;
     }
   };
   std::vector<std::thread> th;

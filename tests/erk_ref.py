@@ -35,7 +35,7 @@ def lib():
         L.erk_load_external_model.argtypes = [C.c_char_p]
         L.erk_solve_to_points.argtypes = [C.c_int, C.c_int, _dp, C.c_int, C.c_double, _dp, C.c_double, C.c_double, _dp, C.c_int, C.c_int, _dp, _lp]
         L.erk_solve_ensemble.argtypes = [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double, _dp, C.c_int, C.c_double, C.c_double, _dp, C.c_int, C.c_int, C.c_int,
-                                         C.c_int, _dp, _dp, _lp, _ip, _dp, _ip, _ip]
+                                         C.c_int, _dp, _dp, _lp, _ip, _dp, _ip, _ip, _dp]
         _lib = L
     return _lib
 
@@ -43,6 +43,21 @@ def lib():
 def _d(a):
     a = np.ascontiguousarray(a, dtype=np.float64)
     return a, a.ctypes.data_as(_dp)
+
+
+OPTION_DEFAULTS = dict(max_error_test_failures=40, min_timestep=1e-13, pi_control_integral=0.5, pi_control_proportional=0.0, max_steps=0)
+
+
+def options_array(options):
+    """the `options` argument of the three *_solve_ensemble entries: None (every default), or the five doubles of SolveOptions (erk_ref.cpp) from a dict of
+    max_error_test_failures, min_timestep, pi_control_integral, pi_control_proportional (the reference's OdeSolverOptions fields ExplicitRk reads) and max_steps (the
+    device ABI's step cap, which the reference does not have; <= 0: 10 000 000)"""
+    if options is None:
+        return None, None
+    unknown = set(options) - set(OPTION_DEFAULTS)
+    if unknown:
+        raise KeyError(f"checker: unknown options {sorted(unknown)}")
+    return _d([float({**OPTION_DEFAULTS, **options}[k]) for k in OPTION_DEFAULTS])
 
 
 def set_det_pow(on):
@@ -84,9 +99,9 @@ def solve_to_points(model, p, t_points, *, model_size=0, rtol=1e-6, atol=(1e-6,)
     return y, dict(steps=cnt[0], error_test_failures=cnt[1], rhs_calls=cnt[2])
 
 
-def solve_ensemble(model, p, t_eval, *, model_size=0, rtol=1e-6, atol=(1e-6,), t0=0.0, h0=1.0, group=1, nthreads=8, steps_cap=0):
+def solve_ensemble(model, p, t_eval, *, model_size=0, rtol=1e-6, atol=(1e-6,), t0=0.0, h0=1.0, group=1, nthreads=8, steps_cap=0, options=None):
     """solve_dense (steps_cap = 0; t_eval the save points) or solve (steps_cap > 0; t_eval = [t_final]) per member (group 1) or per lock-step group of `group`
-    members.  atol: [n] / scalar, or [nsys, n] per member.  Returns dict(y [nsys, cols, n], t [nsys, cols] (steps only), stats [nsys, 5], status, t_root, root_idx, ncols, failed)."""
+    members.  atol: [n] / scalar, or [nsys, n] per member.  options: see options_array.  Returns dict(y [nsys, cols, n], t [nsys, cols] (steps only), stats [nsys, 5], status, t_root, root_idx, ncols, failed)."""
     p = np.ascontiguousarray(p, dtype=np.float64)
     nsys, np_ = p.shape
     n = model_dims(model, model_size)["n"]
@@ -100,7 +115,8 @@ def solve_ensemble(model, p, t_eval, *, model_size=0, rtol=1e-6, atol=(1e-6,), t
     stats = np.zeros((nsys, 5), dtype=np.int64)
     status, ridx, ncols = (np.zeros(nsys, dtype=np.int32) for _ in range(3))
     troot = np.full(nsys, np.nan)
+    o_a, o_p = options_array(options)
     failed = lib().erk_solve_ensemble(model, model_size, nsys, p.ctypes.data_as(_dp), np_, rtol, a_p, rows, t0, h0, te_p, te.size, nthreads, group, steps_cap,
                                       y.ctypes.data_as(_dp), t.ctypes.data_as(_dp), stats.ctypes.data_as(_lp), status.ctypes.data_as(_ip), troot.ctypes.data_as(_dp),
-                                      ridx.ctypes.data_as(_ip), ncols.ctypes.data_as(_ip))
+                                      ridx.ctypes.data_as(_ip), ncols.ctypes.data_as(_ip), o_p)
     return dict(y=y, t=t, stats=stats, status=status, t_root=troot, root_idx=ridx, ncols=ncols, failed=int(failed))

@@ -211,9 +211,38 @@ struct ExplicitRk : SolverBase {
 // status codes of the device kernels (dsh_resident.hpp ResidentStatus): the OdeErr ordinal, 20 for a root batch mismatch
 int status_of(OdeErr e) { return e == OdeErr::RootBatchMismatch ? 20 : (int)e; }
 
+// The options of one ensemble solve, read from the caller's array of kNumSolveOptions doubles (null: every default), handed down per call: the groups of an
+// ensemble run on threads, so nothing here is process-wide.  The first four are the reference's OdeSolverOptions fields that ExplicitRk reads
+// (max_error_test_failures and min_timestep: runge_kutta.rs:843-867 through ExplicitRkConfig, config.rs:141-160; the two controller constants: :466-495 into :1313-1336).
+// max_steps HAS NO COUNTERPART IN THE REFERENCE, whose solve loops run until the stop time, a root or an error: it is the device ABI's own limit
+// (dsh_adaptive_options.max_steps), restated as the kernels document it — one count per step() call, tested before the step (++guard > max_steps), status 99
+// (MaxStepsExceeded), a value <= 0 meaning 10 000 000.
+constexpr int kNumSolveOptions = 5;
+constexpr int kStatusMaxStepsExceeded = 99;
+struct SolveOptions {
+  OdeSolverOptions ode;
+  long max_steps = 10000000;
+  explicit SolveOptions(const double* v) {
+    if (!v) return;
+    ode.max_error_test_failures = (int)v[0];
+    ode.min_timestep = v[1];
+    ode.pi_control_integral = v[2];
+    ode.pi_control_proportional = v[3];
+    if ((long)v[4] > 0) max_steps = (long)v[4];
+  }
+};
+// the step cap of the solve loops below: true when the step may be taken
+struct StepGuard {
+  long guard = 0, max_steps;
+  explicit StepGuard(const SolveOptions& o) : max_steps(o.max_steps) {}
+  bool next() { return !(++guard > max_steps); }
+};
+
 // one problem of `cnt` members (cnt = 1: an independent IVP; cnt > 1: a lock-step batched problem); atol: [n] (natol_rows = 1) or one row per member
-std::unique_ptr<Problem> make_problem(int model_id, int model_size, int cnt, const double* p, int np, double rtol, const double* atol, int natol_rows, double t0, double h0) {
+std::unique_ptr<Problem> make_problem(int model_id, int model_size, int cnt, const double* p, int np, double rtol, const double* atol, int natol_rows, double t0, double h0,
+                                      const SolveOptions& so = SolveOptions(nullptr)) {
   auto pr = std::make_unique<Problem>();
+  pr->ode_options = so.ode;
   std::vector<double> pv(p, p + (size_t)np * cnt);
   pr->eqn = std::make_unique<Eqn>(make_model(model_id, model_size), cnt, pv);
   const int n = pr->n();
@@ -309,10 +338,13 @@ int erk_solve_to_points(int model_id, int model_size, const double* p, int np, d
 // solve_dense (method.rs:467-520) / solve (:227-258, :881-961) for an ensemble: group = 1 every member its own IVP, group = G consecutive groups of G members as one
 // lock-step batched problem each.  steps_cap = 0: states at t_eval, y_out [nsys][nt][n]; steps_cap > 0: t_eval[0] is the final time, every accepted step out,
 // y_out [nsys][steps_cap][n], t_out [nsys][steps_cap] (columns beyond the cap are counted, not stored).  atol [n] (natol_rows = 1) or [nsys][n].
-// stats_out [nsys][5] (steps, 0, 0, error-test failures, 0), status_out / root_t_out (NaN: none) / root_idx_out / ncols_out [nsys].  Returns the number of failed members.
+// stats_out [nsys][5] (steps, 0, 0, error-test failures, 0), status_out / root_t_out (NaN: none) / root_idx_out / ncols_out [nsys].  options: null, or the
+// kNumSolveOptions doubles of SolveOptions (max_error_test_failures, min_timestep, pi_control_integral, pi_control_proportional, max_steps).  Returns the number of
+// failed members.
 int erk_solve_ensemble(int model_id, int model_size, int nsys, const double* p, int np, double rtol, const double* atol, int natol_rows, double t0, double h0,
                        const double* t_eval, int nt, int nthreads, int group, int steps_cap, double* y_out, double* t_out, long* stats_out, int* status_out,
-                       double* root_t_out, int* root_idx_out, int* ncols_out) {
+                       double* root_t_out, int* root_idx_out, int* ncols_out, const double* options) {
+  const SolveOptions so(options);
   if (group < 1) group = 1;
   if (nthreads < 1) nthreads = 1;
   const int ngroups = (nsys + group - 1) / group;
@@ -322,7 +354,7 @@ int erk_solve_ensemble(int model_id, int model_size, int nsys, const double* p, 
   auto work = [&](int tid) {
     for (int g = tid; g < ngroups; g += nthreads) {
       const int s0 = g * group, cnt = std::min(group, nsys - s0);
-      auto pr = make_problem(model_id, model_size, cnt, p + (size_t)s0 * np, np, rtol, natol_rows == 1 ? atol : atol + (size_t)s0 * n_model, natol_rows, t0, h0);
+      auto pr = make_problem(model_id, model_size, cnt, p + (size_t)s0 * np, np, rtol, natol_rows == 1 ? atol : atol + (size_t)s0 * n_model, natol_rows, t0, h0, so);
       const int n = pr->n();
       const int width = steps_cap > 0 ? steps_cap : nt;
       ExplicitRk sv(pr.get(), tsit45());
@@ -341,7 +373,10 @@ int erk_solve_ensemble(int model_id, int model_size, int nsys, const double* p, 
         if (steps_cap > 0) steps_write(sv.t(), sv.y());
         err = sv.set_stop_time(t_eval[nt - 1]);
       }
+      StepGuard cap(so);
+      bool capped = false;
       while (err == OdeErr::Ok) {
+        if (!cap.next()) { capped = true; break; }
         StopReason r;
         err = sv.step(r);
         if (err != OdeErr::Ok) break;
@@ -363,7 +398,7 @@ int erk_solve_ensemble(int model_id, int model_size, int nsys, const double* p, 
         if (ncols_out) ncols_out[m] = col;
         if (steps_cap == 0)
           for (int c2 = col; c2 < nt; ++c2) for (int i = 0; i < n; ++i) y_out[((size_t)m * nt + c2) * n + i] = nan;
-        if (status_out) status_out[m] = status_of(err);
+        if (status_out) status_out[m] = capped ? kStatusMaxStepsExceeded : status_of(err);
         if (root_t_out) root_t_out[m] = rooted ? sv.root_time : nan;
         if (root_idx_out) root_idx_out[m] = rooted ? sv.root_index : -1;
         if (stats_out) {
@@ -371,7 +406,7 @@ int erk_solve_ensemble(int model_id, int model_size, int nsys, const double* p, 
           o[0] = sv.stats().number_of_steps; o[1] = 0; o[2] = 0; o[3] = sv.stats().number_of_error_test_failures; o[4] = 0;
         }
       }
-      if (err != OdeErr::Ok) failed_per_thread[(size_t)tid] += cnt;
+      if (err != OdeErr::Ok || capped) failed_per_thread[(size_t)tid] += cnt;
     }
   };
   std::vector<std::thread> th;

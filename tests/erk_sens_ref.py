@@ -37,7 +37,7 @@ def lib():
         L.erk_load_external_model.argtypes = [C.c_char_p]
         L.erks_solve_to_points.argtypes = [C.c_int, C.c_int, _dp, C.c_int, C.c_double, _dp, C.c_double, C.c_double, C.c_double, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _lp]
         L.erks_solve_ensemble.argtypes = [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double, _dp, C.c_int, C.c_double, C.c_double, C.c_double, _dp, C.c_int, _dp, C.c_int,
-                                          C.c_int, C.c_int, _dp, _dp, _lp, _ip, _lp]
+                                          C.c_int, C.c_int, _dp, _dp, _lp, _ip, _lp, _dp]
         _lib = L
     return _lib
 
@@ -94,8 +94,10 @@ def solve_to_points(model, p, t_points, *, model_size=0, rtol=1e-6, atol=(1e-6,)
     return y, s.transpose(1, 0, 2), dict(steps=cnt[0], error_test_failures=cnt[1], rhs_calls=cnt[2], jac_muls=cnt[3])
 
 
-def solve_ensemble(model, p, t_eval, *, model_size=0, rtol=1e-6, atol=(1e-6,), t0=0.0, h0=1.0, sens_rtol=1e-6, sens_atol=(1e-6,), group=1, nthreads=8):
-    """solve_dense_sensitivities per member (group 1) or per lock-step group of `group` members.  atol: [n] / scalar, or [nsys, n] per member.
+def solve_ensemble(model, p, t_eval, *, model_size=0, rtol=1e-6, atol=(1e-6,), t0=0.0, h0=1.0, sens_rtol=1e-6, sens_atol=(1e-6,), group=1, nthreads=8,
+                   options=None):
+    """solve_dense_sensitivities per member (group 1) or per lock-step group of `group` members.  atol: [n] / scalar, or [nsys, n] per member.  options: see
+    erk_ref.options_array.
     Returns dict(y [nsys, nt, n], sens [nparams, nsys, nt, n], stats [nsys, 5], status [nsys], rhs_calls [nsys], jac_muls [nsys], failed)."""
     p = np.ascontiguousarray(p, dtype=np.float64)
     nsys, np_ = p.shape
@@ -110,8 +112,9 @@ def solve_ensemble(model, p, t_eval, *, model_size=0, rtol=1e-6, atol=(1e-6,), t
     stats = np.zeros((nsys, 5), dtype=np.int64)
     calls = np.zeros((nsys, 2), dtype=np.int64)
     status = np.zeros(nsys, dtype=np.int32)
+    o_a, o_p = erk_ref.options_array(options)
     failed = lib().erks_solve_ensemble(model, model_size, nsys, p.ctypes.data_as(_dp), np_, rtol, a_p, rows, t0, h0, sens_rtol, sa_p, nsa, te_p, te.size, nthreads, group,
-                                       y.ctypes.data_as(_dp), s.ctypes.data_as(_dp), stats.ctypes.data_as(_lp), status.ctypes.data_as(_ip), calls.ctypes.data_as(_lp))
+                                       y.ctypes.data_as(_dp), s.ctypes.data_as(_dp), stats.ctypes.data_as(_lp), status.ctypes.data_as(_ip), calls.ctypes.data_as(_lp), o_p)
     if failed < 0:
         _raise(failed)
     return dict(y=y, sens=np.ascontiguousarray(s.transpose(2, 0, 1, 3)), stats=stats, status=status, rhs_calls=calls[:, 0], jac_muls=calls[:, 1], failed=int(failed))

@@ -134,8 +134,8 @@ struct ExplicitRkSens : ExplicitRk {
 // make_problem of the plain checker plus the sensitivity tolerances (builder.rs build_atols: one vector for every parameter); nsens_atol = 0: the sensitivities stay out of
 // the error control (turn_off_sensitivities_error_control), 1: one value for every state, n: per state
 std::unique_ptr<Problem> make_sens_problem(int model_id, int model_size, int cnt, const double* p, int np, double rtol, const double* atol, int natol_rows, double t0, double h0,
-                                           double sens_rtol, const double* sens_atol, int nsens_atol) {
-  auto pr = make_problem(model_id, model_size, cnt, p, np, rtol, atol, natol_rows, t0, h0);
+                                           double sens_rtol, const double* sens_atol, int nsens_atol, const SolveOptions& so = SolveOptions(nullptr)) {
+  auto pr = make_problem(model_id, model_size, cnt, p, np, rtol, atol, natol_rows, t0, h0, so);
   pr->sens = true;
   pr->sens_error_control = nsens_atol > 0;
   pr->sens_rtol = sens_rtol;
@@ -184,10 +184,11 @@ int erks_solve_to_points(int model_id, int model_size, const double* p, int np, 
 // solve_dense_sensitivities for an ensemble: group = 1 every member its own IVP, group = G consecutive groups of G members as one lock-step batched problem each (the
 // sensitivity norms are max-reduced over the group like the states').  y_out [nsys][nt][n], s_out [nsys][nt][np][n] (columns never reached: NaN), atol [n]
 // (natol_rows = 1) or [nsys][n]; stats_out [nsys][5] (steps, 0, 0, error-test failures, 0), status_out [nsys], calls_out [nsys][2] (right-hand sides, Jacobian
-// products of the member's problem).  Returns the number of failed members, or -101 for a model without parameter derivatives.
+// products of the member's problem).  options: as erk_solve_ensemble's.  Returns the number of failed members, or -101 for a model without parameter derivatives.
 int erks_solve_ensemble(int model_id, int model_size, int nsys, const double* p, int np, double rtol, const double* atol, int natol_rows, double t0, double h0, double sens_rtol,
                         const double* sens_atol, int nsens_atol, const double* t_eval, int nt, int nthreads, int group, double* y_out, double* s_out, long* stats_out,
-                        int* status_out, long* calls_out) {
+                        int* status_out, long* calls_out, const double* options) {
+  const SolveOptions so(options);
   if (group < 1) group = 1;
   if (nthreads < 1) nthreads = 1;
   {
@@ -202,7 +203,7 @@ int erks_solve_ensemble(int model_id, int model_size, int nsys, const double* p,
     for (int g = tid; g < ngroups; g += nthreads) {
       const int s0 = g * group, cnt = std::min(group, nsys - s0);
       auto pr = make_sens_problem(model_id, model_size, cnt, p + (size_t)s0 * np, np, rtol, natol_rows == 1 ? atol : atol + (size_t)s0 * n_model, natol_rows, t0, h0, sens_rtol,
-                                  sens_atol, nsens_atol);
+                                  sens_atol, nsens_atol, so);
       const int n = pr->n();
       ExplicitRkSens sv(pr.get(), tsit45());
       int col = 0;
@@ -210,7 +211,10 @@ int erks_solve_ensemble(int model_id, int model_size, int nsys, const double* p,
       V tmp(n, cnt);
       std::vector<V> stmp((size_t)np, V(n, cnt));
       if (err == OdeErr::Ok) err = sv.set_stop_time(t_eval[nt - 1]);
+      StepGuard cap(so);
+      bool capped = false;
       while (err == OdeErr::Ok) {
+        if (!cap.next()) { capped = true; break; }
         StopReason r;
         err = sv.step(r);
         if (err != OdeErr::Ok) break;
@@ -231,14 +235,14 @@ int erks_solve_ensemble(int model_id, int model_size, int nsys, const double* p,
           for (int i = 0; i < n; ++i) y_out[((size_t)m * nt + c2) * n + i] = nan;
           for (int i = 0; i < np * n; ++i) s_out[((size_t)m * nt + c2) * np * n + i] = nan;
         }
-        if (status_out) status_out[m] = status_of(err);
+        if (status_out) status_out[m] = capped ? kStatusMaxStepsExceeded : status_of(err);
         if (stats_out) {
           long* o = stats_out + (size_t)m * 5;
           o[0] = sv.stats().number_of_steps; o[1] = 0; o[2] = 0; o[3] = sv.stats().number_of_error_test_failures; o[4] = 0;
         }
         if (calls_out) { calls_out[(size_t)m * 2] = pr->eqn->rhs_stats.calls; calls_out[(size_t)m * 2 + 1] = pr->eqn->rhs_stats.jac_muls; }
       }
-      if (err != OdeErr::Ok) failed_per_thread[(size_t)tid] += cnt;
+      if (err != OdeErr::Ok || capped) failed_per_thread[(size_t)tid] += cnt;
     }
   };
   std::vector<std::thread> th;

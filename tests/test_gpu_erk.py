@@ -67,12 +67,14 @@ CASES = {
 }
 
 
-def device_solve(H, model, size, p, t_eval, rtol, atol, group, steps_cap=0):
-    """dsh_erk_solve_resident[_steps] through the device C ABI (per-member atol travels only there).  atol [n] or [nb, n]."""
+def device_solve(H, model, size, p, t_eval, rtol, atol, group, steps_cap=0, t0=0.0, h0=1.0, options=None):
+    """dsh_erk_solve_resident[_steps] through the device C ABI (per-member atol travels only there).  atol [n] or [nb, n]; options: fields of dsh_adaptive_options
+    to set over the defaults."""
     from diffsol_amd import _ffi
     dev = _ffi.load_device_lib()
     c = _ffi.vp()
     _ffi.check(dev.dsh_ctx_create(0, None, C.byref(c)))
+    bufs = {}
     try:
         nb, npar = p.shape
         info = [C.c_int64(), C.c_int64(), C.c_int(), C.c_int64()]
@@ -83,7 +85,6 @@ def device_solve(H, model, size, p, t_eval, rtol, atol, group, steps_cap=0):
         a_host = np.ascontiguousarray(at.T if at.ndim == 2 else at)   # device layout: n x nb, batch-fastest
         p_host = np.ascontiguousarray(p.T)
         cols = steps_cap if steps_cap else len(t_eval)
-        bufs = {}
 
         def dmalloc(name, nbytes):
             q = _ffi.vp()
@@ -97,14 +98,17 @@ def device_solve(H, model, size, p, t_eval, rtol, atol, group, steps_cap=0):
         o = AdaptiveOptions()
         dev.dsh_adaptive_default_options(C.byref(o))
         o.deterministic_pow, o.group = 1, group
+        for k, v in (options or {}).items():
+            getattr(o, k)   # an unknown field is an error, not a new attribute
+            setattr(o, k, v)
         opts = C.cast(C.pointer(o), C.c_void_p)
         tot = (C.c_int64 * 6)()
         te = np.ascontiguousarray(t_eval, dtype=float)
         if steps_cap:
-            rc = dev.dsh_erk_solve_resident_steps(c, 3, model, size, nb, bufs["p"], bufs["atol"], atol_nb, rtol, 0.0, 1.0, opts, float(te[-1]), steps_cap, bufs["y"], bufs["t"],
+            rc = dev.dsh_erk_solve_resident_steps(c, 3, model, size, nb, bufs["p"], bufs["atol"], atol_nb, rtol, t0, h0, opts, float(te[-1]), steps_cap, bufs["y"], bufs["t"],
                                                   bufs["stats"], bufs["status"], bufs["troot"], bufs["ridx"], bufs["ncols"], tot)
         else:
-            rc = dev.dsh_erk_solve_resident(c, 3, model, size, nb, bufs["p"], bufs["atol"], atol_nb, rtol, 0.0, 1.0, opts, te.ctypes.data_as(_ffi.c_dp), te.size, bufs["y"],
+            rc = dev.dsh_erk_solve_resident(c, 3, model, size, nb, bufs["p"], bufs["atol"], atol_nb, rtol, t0, h0, opts, te.ctypes.data_as(_ffi.c_dp), te.size, bufs["y"],
                                             bufs["stats"], bufs["status"], bufs["troot"], bufs["ridx"], bufs["ncols"], tot)
         _ffi.check(rc)
 

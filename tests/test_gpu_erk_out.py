@@ -85,9 +85,9 @@ def params(name, nb, group):
     return draw(nb)
 
 
-def device_solve(model, size, nout, p, t_eval, rtol, atol, group, out_rtol=0.0, out_atol=None, steps_cap=0, expect=None):
+def device_solve(model, size, nout, p, t_eval, rtol, atol, group, out_rtol=0.0, out_atol=None, steps_cap=0, expect=None, t0=0.0, h0=1.0, options=None):
     """dsh_erk_solve_resident_out / _steps_out through the device C ABI.  atol [n] or [nb, n]; out_atol None (outside the error test) or a list.  expect: the error code
-    the call must return (the message comes back instead of the arrays)."""
+    the call must return (the message comes back instead of the arrays).  options: fields of dsh_adaptive_options to set over the defaults."""
     from diffsol_amd import _ffi
     dev = _ffi.load_device_lib()
     c = _ffi.vp()
@@ -113,17 +113,20 @@ def device_solve(model, size, nout, p, t_eval, rtol, atol, group, out_rtol=0.0, 
         o = AdaptiveOptions()
         dev.dsh_adaptive_default_options(C.byref(o))
         o.deterministic_pow, o.group = 1, group
+        for k, v in (options or {}).items():
+            getattr(o, k)   # an unknown field is an error, not a new attribute
+            setattr(o, k, v)
         opts = C.cast(C.pointer(o), C.c_void_p)
         tot = (C.c_int64 * 6)()
         te = np.ascontiguousarray(t_eval, dtype=float)
         oa = np.ascontiguousarray(np.zeros(1) if out_atol is None else np.asarray(out_atol, dtype=float).reshape(-1))
         noa = 0 if out_atol is None else oa.size
         if steps_cap:
-            rc = dev.dsh_erk_solve_resident_steps_out(c, 3, model, size, nb, bufs["p"], bufs["atol"], atol_nb, rtol, 0.0, 1.0, opts, float(te[-1]), steps_cap, out_rtol,
+            rc = dev.dsh_erk_solve_resident_steps_out(c, 3, model, size, nb, bufs["p"], bufs["atol"], atol_nb, rtol, t0, h0, opts, float(te[-1]), steps_cap, out_rtol,
                                                       oa.ctypes.data_as(_ffi.c_dp), noa, bufs["y"], bufs["t"], bufs["stats"], bufs["status"], bufs["troot"], bufs["ridx"],
                                                       bufs["ncols"], tot)
         else:
-            rc = dev.dsh_erk_solve_resident_out(c, 3, model, size, nb, bufs["p"], bufs["atol"], atol_nb, rtol, 0.0, 1.0, opts, te.ctypes.data_as(_ffi.c_dp), te.size, out_rtol,
+            rc = dev.dsh_erk_solve_resident_out(c, 3, model, size, nb, bufs["p"], bufs["atol"], atol_nb, rtol, t0, h0, opts, te.ctypes.data_as(_ffi.c_dp), te.size, out_rtol,
                                                 oa.ctypes.data_as(_ffi.c_dp), noa, bufs["y"], bufs["stats"], bufs["status"], bufs["troot"], bufs["ridx"], bufs["ncols"], tot)
         if expect is not None:
             assert rc == expect, (rc, dev.dsh_last_error())

@@ -45,9 +45,10 @@ def det_pow():
     S.set_det_pow(False)
 
 
-def device_solve(model, size, p, t_eval, rtol, atol, group, sens=True, sens_rtol=1e-6, sens_atol=(1e-6,), max_steps=None):
+def device_solve(model, size, p, t_eval, rtol, atol, group, sens=True, sens_rtol=1e-6, sens_atol=(1e-6,), max_steps=None, t0=0.0, h0=1.0,
+                 options=None):
     """dsh_erk_solve_resident_sens (sens=True) or dsh_erk_solve_resident through the device C ABI: per-member atol and max_steps travel only there.  atol [n] or
-    [nb, n]; sens_atol None: out of the error control.  Returns dict(y [nb, nt, n], sens [np, nb, nt, n], stats [nb, 5], status [nb], totals)."""
+    [nb, n]; sens_atol None: out of the error control; options: fields of dsh_adaptive_options to set over the defaults.  Returns dict(y [nb, nt, n], sens [np, nb, nt, n], stats [nb, 5], status [nb], totals)."""
     from diffsol_amd import _ffi
     L = _ffi.load_device_lib()
     c = _ffi.vp()
@@ -75,16 +76,19 @@ def device_solve(model, size, p, t_eval, rtol, atol, group, sens=True, sens_rtol
         o.deterministic_pow, o.group = 1, group
         if max_steps is not None:
             o.max_steps = max_steps
+        for k, v in (options or {}).items():
+            getattr(o, k)   # an unknown field is an error, not a new attribute
+            setattr(o, k, v)
         opts = C.cast(C.pointer(o), C.c_void_p)
         tot = (C.c_int64 * 6)()
         te = np.ascontiguousarray(t_eval, dtype=float)
         if sens:
             sa = np.zeros(1) if sens_atol is None else np.ascontiguousarray(np.asarray(sens_atol, dtype=float).reshape(-1))
-            rc = L.dsh_erk_solve_resident_sens(c, 3, model, size, nb, bufs["p"], bufs["atol"], nb if at.ndim == 2 else 1, rtol, 0.0, 1.0, opts, te.ctypes.data_as(_ffi.c_dp),
+            rc = L.dsh_erk_solve_resident_sens(c, 3, model, size, nb, bufs["p"], bufs["atol"], nb if at.ndim == 2 else 1, rtol, t0, h0, opts, te.ctypes.data_as(_ffi.c_dp),
                                                te.size, sens_rtol, sa.ctypes.data_as(_ffi.c_dp), 0 if sens_atol is None else sa.size, bufs["y"], bufs["sens"], bufs["stats"],
                                                bufs["status"], tot)
         else:
-            rc = L.dsh_erk_solve_resident(c, 3, model, size, nb, bufs["p"], bufs["atol"], nb if at.ndim == 2 else 1, rtol, 0.0, 1.0, opts, te.ctypes.data_as(_ffi.c_dp),
+            rc = L.dsh_erk_solve_resident(c, 3, model, size, nb, bufs["p"], bufs["atol"], nb if at.ndim == 2 else 1, rtol, t0, h0, opts, te.ctypes.data_as(_ffi.c_dp),
                                           te.size, bufs["y"], bufs["stats"], bufs["status"], None, None, None, tot)
         _ffi.check(rc)
 

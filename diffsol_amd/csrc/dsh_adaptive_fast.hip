@@ -26,6 +26,12 @@
 // the identity on what these call sites reduce.  The stage is exact under their conditions: the values are weighted mean squares (never negative), a ballot ahead of
 // the chain has excluded a NaN (a wavefront that holds one takes the two-pass bit-pattern maximum, unchanged), and all 64 lanes are active.  IEEE mode stays on, so
 // every other fmax / fmin keeps its instructions.  Same values: still the general fast kernel's bits (profiles/wave_max_raw.md, tests/test_gpu_wave_max_raw.py).
+// Its step loop reloads nothing from scratch (DSH_STEP_NO_RELOAD, dsh_adaptive_kernel.hpp): the next save point is a wavefront-uniform value that is NaN behind
+// the last column, so the save-point test of a step is one comparison on a value in scalar registers, with no scratch reload and no load of n_eval per step, and the
+// lane-dependent invariants the compiler formed ahead of the loop and spilled (the lane's role in the order selection's shared pow, the R column of the Newton
+// failure's constant factor) are formed where they are read.  Scratch falls from 80 to 32 B in the instantiation bench.py times; the three reloads left are on the
+// path that writes a column and behind the loop.  Same values: still the general fast kernel's bits (profiles/pivot_facts.md, tests/test_gpu_pivot_facts.py,
+// tests/test_pivot_facts.py).  That document also records the pivot facts that were built, measured slower and left out.
 //
 // Its results are NOT bit-comparable with the oracle (every other kernel of the library is); north_star asks for 1e-6 relative on the states,
 // which the tests hold it to at tight tolerances; at the bench's full size it makes the step decisions of the exact kernel (every member's five counters equal,

@@ -367,6 +367,12 @@ __device__ __forceinline__ double inv_root_2k_group(double x, int k, double expo
 #ifndef DSH_PAIR_PRIO_HIGH
 #define DSH_PAIR_PRIO_HIGH 5
 #endif
+// No spill reload on the step loop's paths of the lock-step fast kernel with the default options (LOCKFAST in k_bdf_adaptive; profiles/pivot_facts.md): the next save point as a wavefront-uniform value that is NaN once the
+// last column is out (one comparison decides "a column is due", no load of n_eval per step), and lane-dependent loop invariants formed where they are read instead
+// of once at the head of the kernel, where they were spilled.  DSH_STEP_NO_RELOAD=0: the parent's instructions.
+#ifndef DSH_STEP_NO_RELOAD
+#define DSH_STEP_NO_RELOAD 1
+#endif
 // the phase of the policy is wavefront-uniform by construction; s_setprio ignores EXEC, so each one sits alone behind a scalar branch on a readfirstlane value
 __device__ __forceinline__ void pair_prio_set(unsigned phase_bits) {
   if (__builtin_amdgcn_readfirstlane(phase_bits & 1u) != 0) __builtin_amdgcn_s_setprio(1);
@@ -393,6 +399,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DSH_ADAPTIVE
   const AdaptiveConsts& C = *Cp;
   constexpr bool kPairPrio = LOCKFAST && DSH_PAIR_PRIO != 0;
   constexpr bool kRawMax = LOCKFAST && DSH_RAW_WAVE_MAX != 0;                // its wavefront maxima by dpp_max_f64_raw (above)
+  constexpr bool kNoReload = LOCKFAST && DSH_STEP_NO_RELOAD != 0;            // DSH_STEP_NO_RELOAD above
   static_assert((DSH_PAIR_PRIO_PERIOD & (DSH_PAIR_PRIO_PERIOD - 1)) == 0 && DSH_PAIR_PRIO_PERIOD > 0, "DSH_PAIR_PRIO_PERIOD: a power of two");
   static_assert(DSH_PAIR_PRIO_HIGH >= 0 && DSH_PAIR_PRIO_HIGH < 2 * DSH_PAIR_PRIO_PERIOD, "DSH_PAIR_PRIO_HIGH: trips of the 2 x DSH_PAIR_PRIO_PERIOD");
   // the wavefront's role in the policy (DSH_PAIR_PRIO above): 0 = no policy in this launch, no s_setprio; 1 = a wavefront of the first round of the dispatch (the
@@ -604,7 +611,10 @@ DSH_UNROLL_N
       // entry by the operations, in the order, of the sequential code, so the bits are the same; then every lane applies R U to its own differences.
       const int ou = __builtin_amdgcn_readfirstlane(order);
       {
-        const int m = ln & 7;  // lanes 0..5: column m
+        int m = ln & 7;  // lanes 0..5: column m
+        // DSH_STEP_NO_RELOAD above: for a factor that is a constant (the Newton failure's) the whole column is loop-invariant; it was formed ahead of the step loop,
+        // spilled, and reloaded here from scratch.  Behind the empty asm it is formed here, like the column of any other factor.
+        if constexpr (kNoReload) asm volatile("" : "+v"(m));
         double r = 1.0;
         sRw[m * 6 + 0] = r;
 #pragma unroll
@@ -848,6 +858,10 @@ DSH_UNROLL_N
 
   int col = 0;
   double te_next = t_eval[0];  // t_eval[col], kept in a register: it is compared after every step
+  // DSH_STEP_NO_RELOAD above: wavefront-uniform (scalar registers, or lanes of the scalar spill register: no scratch), and NaN when no column is left, so that
+  // `te_next <= upto` alone is the parent's `col < n_eval && te_next <= upto` for every input: with a column left it is the same comparison (a NaN save point or a
+  // NaN time compares false in both), with none left both are false
+  if constexpr (kNoReload) te_next = uniform<WAVE>(0 < C.r.n_eval ? te_next : __builtin_nan(""));
   const bool steps_mode = !SEG && !SENS && C.steps_cap > 0;  // every accepted step out (see AdaptiveConsts::steps_cap)
   auto steps_write = [&](double tw, const double (&yw)[N]) __attribute__((always_inline)) {
     if (col < C.steps_cap && active) {
@@ -1390,7 +1404,15 @@ DSH_UNROLL_N
         // (base, exponent) pair each and ONE call of pow serves all of them — the same function on the same arguments, so the same bits, for a sixth
         // (or a third) of the instructions; v_readlane brings the results back
         const bool two = (pi_p != 0.0) & has_prev_err;
-        const int l6 = ln & 7, which = l6 >> 1;
+        int lnq = ln;
+        // DSH_STEP_NO_RELOAD above: the lane's role was formed ahead of the step loop and spilled; held behind an empty asm it is the lane index that is spilled instead.
+        // So the lane index is counted here (v_mbcnt_lo / _hi over a zero the compiler cannot see through: a workgroup is one wavefront, threadIdx.x is the lane)
+        if constexpr (kNoReload) {
+          unsigned z = 0u;
+          asm volatile("" : "+v"(z));
+          lnq = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
+        }
+        const int l6 = lnq & 7, which = l6 >> 1;
         const double eo = (double)(order + which);
         const double ki = pi_i / eo, kp = pi_p / eo;
         const double errs = which == 0 ? error_m_norm : (which == 1 ? error_norm : error_p_norm);
@@ -1457,7 +1479,7 @@ DSH_UNROLL_N
     if (steps_mode) {  // OdeSolverMethod::solve: InternalTimestep / TstopReached -> write_out (method.rs:907-921); a root is written below, at the root
       if (reason != 3) steps_write(t, y);  // state.y (the converged Newton iterate), not D[0] (the same value summed in another order)
     } else
-    while (col < C.r.n_eval && te_next <= upto) {
+    while ((kNoReload || col < C.r.n_eval) && te_next <= upto) {
       double yv[N];
       interpolate(te_next, yv);
 DSH_UNROLL_N
@@ -1482,6 +1504,8 @@ DSH_UNROLL_N
         }
       }
       col++;
+      if constexpr (kNoReload) te_next = uniform<WAVE>(col < C.r.n_eval ? t_eval[col] : __builtin_nan(""));
+      else
       if (col < C.r.n_eval) te_next = t_eval[col];
     }
     if constexpr (kResets) {

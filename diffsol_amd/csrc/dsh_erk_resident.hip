@@ -11,8 +11,8 @@
 // fast-arithmetic twin: deterministic_pow = 2 runs this kernel with the portable pow, like 1.
 //
 // Two trailing template flags add to the lane's state, each for the models its admission function takes: SENS the forward sensitivities of every parameter
-// (dsh_erk_solve_resident_sens), INTOUT the integral g of the output equations, returned in place of the states (dsh_erk_solve_resident_out / _steps_out; checker
-// tests/erk_out_ref/erk_out_ref.cpp).  With both off the kernel is the plain one: the same instructions in the same order, the same registers and code length; since the
+// (dsh_erk_solve_resident_sens), INTOUT the integral g of the output equations, returned in place of the states (dsh_erk_solve_resident_out / _steps_out); the
+// checker has the same two as modes of its one integrator.  With both off the kernel is the plain one: the same instructions in the same order, the same registers and code length; since the
 // folds moved into helpers a few commutative operands are swapped and a few literals enter with the other sign and are subtracted (profiles/erk_kernel_refactor.md).
 #include <cmath>
 #include <cstring>

@@ -33,6 +33,8 @@ def det_pow(request):
 @pytest.mark.parametrize("model,size,t_eval,rtol,atol", [("exponential_decay", 0, [0.5, 1.0, 2.5, 6.0], 1e-6, [1e-6, 1e-6]),
                                                          ("robertson_ode", 1, [1e-4, 1e-3, 4e-3], 1e-4, [1e-8, 1e-14, 1e-6])])
 def test_off_is_the_plain_checker_bit_for_bit(det_pow, model, size, t_eval, rtol, atol, group):
+    """With integrate_out off both sides now run the same code of the one checker, so that half proves less than it did when they were two programs; what the checker
+    computed then is held by the recorded hashes of tests/test_erk_checker_parity.py.  The half with integrate_out on still compares two modes"""
     rng = np.random.default_rng(5)
     nb = 7
     if model == "exponential_decay":

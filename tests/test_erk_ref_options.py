@@ -35,16 +35,16 @@ def det_pow():
         m.set_det_pow(False)
 
 
-_twin = {}
+_twin = []
 
 
-def blow_up(mod):
-    """the checker's id of DYDT_Y2's host twin in the library of `mod` (each checker library has its own registry)"""
-    if mod not in _twin:
+def blow_up():
+    """the checker's id of DYDT_Y2's host twin (one registry behind the three modules)"""
+    if not _twin:
         import diffsl_models as DM
         so, _ = DM.host_model_so(DYDT_Y2)
-        _twin[mod] = mod.load_external_model(so)
-    return _twin[mod]
+        _twin.append(E.load_external_model(so))
+    return _twin[0]
 
 
 def columns(r):
@@ -71,7 +71,7 @@ def test_no_options_and_the_default_options_are_the_same_run(mod):
 def test_the_blow_up_reaches_the_rejection_branch_with_default_options():
     """explicit_rk.rs:227-239: a rejected attempt multiplies h by the factor, forgets the previous error norm and counts a failure.  Behind the blow-up every attempt
     is rejected until one of error_test_fail's two exits (runge_kutta.rs:843-867) is taken; the columns before it are written, the others NaN"""
-    r = E.solve_ensemble(blow_up(E), P1, T_BLOW, options=dict(max_steps=100000), **TOL)
+    r = E.solve_ensemble(blow_up(), P1, T_BLOW, options=dict(max_steps=100000), **TOL)
     assert r["status"][0] in (1, 2) and r["failed"] == 1 and r["stats"][0, 3] > 0
     assert r["ncols"][0] == 3 and np.isfinite(r["y"][0, :3]).all() and np.isnan(r["y"][0, 3:]).all()
     exact = 1.0 / (1.0 / np.array([1.0, 2.0, 0.5])[None, :] - np.array(T_BLOW[:3])[:, None])
@@ -82,7 +82,7 @@ def test_the_blow_up_reaches_the_rejection_branch_with_default_options():
 def test_max_error_test_failures_1_fails_at_the_first_rejection(mod):
     """runge_kutta.rs:852-859: `nattempts >= max_error_test_fails` with nattempts already counted (explicit_rk.rs:228), so a limit of 1 fails at the first rejected
     attempt, with exactly one counted failure (:850).  Up to there the run is the unrestricted one: its columns bit for bit, NaN behind them"""
-    mid = blow_up(mod)
+    mid = blow_up()
     free = mod.solve_ensemble(mid, P1, T_BLOW, options=dict(max_steps=100000), **TOL)
     one = mod.solve_ensemble(mid, P1, T_BLOW, options=dict(max_steps=100000, max_error_test_failures=1), **TOL)
     assert free["stats"][0, 3] > 1
@@ -101,7 +101,7 @@ def test_max_error_test_failures_1_fails_at_the_first_rejection(mod):
 def test_the_failure_count_is_tested_before_the_step_size(mod):
     """runge_kutta.rs:852 comes before :861: with both limits violated at the first rejection the error is TooManyErrorTestFailures (2); the step-size limit alone
     gives StepSizeTooSmall (1) at the same rejection.  min_timestep is read nowhere else: a huge one changes nothing before the first rejection"""
-    mid = blow_up(mod)
+    mid = blow_up()
     both = mod.solve_ensemble(mid, P1, T_BLOW, options=dict(max_steps=100000, max_error_test_failures=1, min_timestep=1e30), **TOL)
     small = mod.solve_ensemble(mid, P1, T_BLOW, options=dict(max_steps=100000, min_timestep=1e30), **TOL)
     assert both["status"][0] == 2 and small["status"][0] == 1

@@ -110,6 +110,16 @@ def test_checker_stays_under_the_bound_on_the_gpu_accuracy_ranges(group):
     assert (r["jac_muls"] == 2 + 12 * (r["stats"][:, 0] + r["stats"][:, 3])).all()
 
 
+def test_sensitivities_of_a_model_with_root_functions_are_refused():
+    """the checker does not restate sensitivities across a root, and the device refuses the combination: both entries say so rather than integrating past the root"""
+    root, p = ORACLE_MODEL["exponential_decay_with_root"], np.array([[0.5, 1.0], [1.0, 2.0]])   # both members cross 0.6 before t = 4
+    with pytest.raises(RuntimeError, match="sensitivities with root functions are not restated"):
+        S.solve_ensemble(root, p, SWEEP_T)
+    with pytest.raises(RuntimeError, match="sensitivities with root functions are not restated"):
+        S.solve_to_points(root, p[0], SWEEP_T)
+    assert (E.solve_ensemble(root, p, SWEEP_T)["root_idx"] == 0).all()   # the plain mode takes the model and stops at its root
+
+
 def test_device_library_admission_rule_and_exports():
     """dsh_erk_model_has_sens: N (14 + 12 NP) <= 112 doubles per lane, parameter derivatives, no root functions, on top of dsh_model_has_resident(3, ..)"""
     from diffsol_amd import MODELS, _ffi

@@ -51,18 +51,18 @@ _TEXTS = {"dydt_y2": P.DYDT_Y2, "osc_out": PO.OSC_OUT, "transcendental": OSM.TRA
 
 
 def model_of(H, name):
-    """dict(dev, size, ref {checker module: id}, nout) of a built-in model or of one of the DiffSL texts above (compiled once per session, its host twin loaded
-    into the registry of each checker library)"""
+    """dict(dev, size, ref (the checker's id), nout) of a built-in model or of one of the DiffSL texts above (compiled once per session, its host twin loaded
+    into the registry of the checker library)"""
     if name not in _models:
         if name not in _TEXTS:   # (the registry has a run-time-sized dydt_y2 of its own: the texts go first)
-            _models[name] = dict(dev=H.MODELS[name], size=0, ref={m: ORACLE_MODEL[name] for m in (E, S, EO)}, keep=None)
+            _models[name] = dict(dev=H.MODELS[name], size=0, ref=ORACLE_MODEL[name], keep=None)
         else:
             import diffsl_models as DM
             from diffsol_amd import diffsl
             m = diffsl.DiffslModel(_TEXTS[name])
             so, _ = DM.host_model_so(_TEXTS[name])
-            _models[name] = dict(dev=m.model_id, size=0, ref={mod: mod.load_external_model(so) for mod in (E, S, EO)}, keep=m)
-        _models[name]["nout"] = EO.model_dims(_models[name]["ref"][EO])["nout"]
+            _models[name] = dict(dev=m.model_id, size=0, ref=E.load_external_model(so), keep=m)
+        _models[name]["nout"] = EO.model_dims(_models[name]["ref"])["nout"]
     return _models[name]
 
 
@@ -78,14 +78,14 @@ def solve_pair(H, entry, name, p, t_eval, group, *, rtol, atol, t0=0.0, h0=1.0, 
     te = [t_eval[-1]] if steps else list(t_eval)
     if entry in ("plain", "steps"):
         dev = P.device_solve(H, m["dev"], m["size"], p, te, rtol, atol, group, steps_cap=cap, t0=t0, h0=h0, options=dopt)
-        ref = E.solve_ensemble(m["ref"][E], p, te, steps_cap=cap, **kw) if reference else None
+        ref = E.solve_ensemble(m["ref"], p, te, steps_cap=cap, **kw) if reference else None
         return dev, ref, "y"
     if entry == "sens":
         dev = PS.device_solve(m["dev"], m["size"], p, te, rtol, atol, group, sens_atol=sens_atol, t0=t0, h0=h0, options=dopt)
-        ref = S.solve_ensemble(m["ref"][S], p, te, sens_atol=sens_atol, **kw) if reference else None
+        ref = S.solve_ensemble(m["ref"], p, te, sens_atol=sens_atol, **kw) if reference else None
         return dev, ref, "y"
     dev = PO.device_solve(m["dev"], m["size"], m["nout"], p, te, rtol, atol, group, steps_cap=cap, t0=t0, h0=h0, options=dopt)
-    ref = EO.solve_ensemble(m["ref"][EO], p, te, steps_cap=cap, **kw) if reference else None
+    ref = EO.solve_ensemble(m["ref"], p, te, steps_cap=cap, **kw) if reference else None
     return dev, ref, "g"
 
 
@@ -151,7 +151,7 @@ def test_a_start_time_other_than_zero(H, t0, at_t0, group):
                 dev, ref, key = solve_pair(H, entry, name, p, t_eval, group, rtol=1e-6, atol=[1e-8] * (3 if name == "osc_out" else 2), t0=t0)
                 assert ref["failed"] == 0 and not ref["status"].any()
                 if entry == "out":   # the case is about t0: the same save points counted from zero give another integral
-                    zero = EO.solve_ensemble(model_of(H, name)["ref"][EO], p, [t - t0 for t in t_eval], rtol=1e-6, atol=[1e-8] * 3, group=group)
+                    zero = EO.solve_ensemble(model_of(H, name)["ref"], p, [t - t0 for t in t_eval], rtol=1e-6, atol=[1e-8] * 3, group=group)
                     assert not np.array_equal(zero["g"][:, -1], ref["g"][:, -1])
                     assert np.array_equal(ref["g"][:, 0] == 0.0, np.full((nb, 1), at_t0))
                 assert_exits_same(dev, ref, key, steps=entry.startswith("steps"))
